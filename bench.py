@@ -13,13 +13,19 @@ Multi-GPU: one process per GPU (torchrun), each rank classifies its own 1 M
 packet shard (weak scaling, no data-path collective); the timed region is
 bracketed by barrier + synchronize and the max over ranks is taken.
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+steps, writes the last step's records if `--dump-outputs DIR` is given and
+prints the result line -- nothing else.  Every other leg (oracle parity, the
+two-stream pass, end-to-end and receive rates, the CPU baseline, the extra
+configurations) runs only with `--full`.
+
 `value` comes from ONE HIP stream: K launches back to back, so the kernel's
 single-launch time (`roofline.kernel_ms`, HIP events on that same stream over
 the same K launches) is never longer than `ms_per_step`.  A two-stream pass
 (consecutive batches alternating over two streams, as a receive path with two
 bursts in flight runs them) is reported as `pipelined` only.
 
-Extra fields on the JSON line:
+Extra fields on the JSON line (all but `roofline` only with `--full`):
   roofline      HBM roofline of the dominant kernel: algorithmic bytes
                 (min(len,128) + 6 B descriptor + 16 B result per packet) over
                 the average launch duration; `traffic` = HBM bytes per launch
@@ -44,6 +50,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s
 N_SIMD = 256 * 4           # 256 CUs x 4 SIMDs
 SCLK_GHZ = 2.4             # peak engine clock
+DUMP_MAX_ROWS = 1_000_000  # --dump-outputs: packets written (40 B each as .npy)
 WORKLOAD = {2: "config2", 3: "config3", 4: "config4", 5: "config5", 33: "config3_64B",
             1: "config1", 20: "config2_norules", 34: "config3_64rules",
             35: "config3_sctp", 36: "config3_nested", 37: "config3_nested1024",
@@ -67,6 +74,15 @@ def parse_args():
     ap.add_argument("--n", "--packets", dest="n", type=int, default=1_000_000,
                     help="packets per GPU (spell it --packets under torchrun, which would "
                          "take --n as an abbreviation of its own options)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg: oracle parity, the two-stream pass, "
+                         "end-to-end and receive rates, the CPU baseline and the extra "
+                         "configurations (a plain run only times the headline steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records the last timed step "
+                         "produced to DIR/<field>.npy (one float32 / float64 array per "
+                         "record field; rank 0's batch, a fixed sample of it above 1 M "
+                         "packets)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
@@ -78,7 +94,8 @@ def parse_args():
                          "file: the main process runs them in a child process, so a failure "
                          "there cannot cost the headline line")
     ap.add_argument("--timed-only", action="store_true",
-                    help="only the timed single-config pass (profiling runs)")
+                    help="only the timed single-config pass, whatever --full says "
+                         "(profiling runs)")
     ap.add_argument("--pktin-opt", type=lambda x: int(x, 0), default=0,
                     help="pktin checksum/drop option bits for the main line (profiling the "
                          "checksum path: 0x3C); valid checksums are written into the batch")
@@ -88,7 +105,10 @@ def parse_args():
                     help="distinct device copies of the batch, used round-robin, so the "
                          "working set (R x batch) exceeds the 256 MiB Infinity Cache and every "
                          "step reads its packets from HBM")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def make_workload(cfg, n, rank):
@@ -132,10 +152,11 @@ def to_device(batch, dev):
 
 
 def time_device(c, batch, dev, steps, warmup, dist_on=False, rotate=1, streams=1):
-    """Warmup, then time `steps` launches; returns (wall_s, avg_kernel_ms, out tensor).
-    With rotate > 1 the launches cycle over that many device copies of the
-    batch (and of the result array), so consecutive steps do not re-read
-    the same bytes from the Infinity Cache."""
+    """Warmup, then time `steps` launches; returns (wall_s, avg_kernel_ms, out tensor):
+    the result array the last timed launch wrote.  With rotate > 1 the
+    launches cycle over that many device copies of the batch (and of the
+    result array), so consecutive steps do not re-read the same bytes from
+    the Infinity Cache."""
     import torch
     import torch.distributed as dist
     copies = [to_device(batch, dev)]
@@ -152,7 +173,6 @@ def time_device(c, batch, dev, steps, warmup, dist_on=False, rotate=1, streams=1
     arglist = [(cb.data_ptr(), co.data_ptr(), cl.data_ptr(), batch.n, cout.data_ptr(),
                 strm[i % len(strm)].cuda_stream)
                for i, (cb, co, cl, cout) in enumerate(copies)]
-    t_out = copies[0][3]
     for i in range(warmup):
         rc = c.classify_device(*arglist[i % len(arglist)])
         assert rc == 0, rc
@@ -181,17 +201,34 @@ def time_device(c, batch, dev, steps, warmup, dist_on=False, rotate=1, streams=1
         dist.barrier()
     wall = time.perf_counter() - t0
     kms = ev0.elapsed_time(ev1) / steps
-    # the last launch on copy 0 wrote t_out: rerun it so the returned records
-    # belong to copy 0's batch whatever `steps` was
-    c.classify_device(*arglist[0])
-    torch.cuda.synchronize(dev)
-    return wall, kms, t_out
+    # every copy holds the same batch: the last timed launch's result array
+    # is what a caller of that launch receives
+    return wall, kms, copies[(steps - 1) % len(copies)][3]
 
 
 def records(t_out, n):
     import numpy as np
     from odp_amd import rules as R
     return t_out.cpu().numpy().view(np.uint8).reshape(-1)[: 16 * n].view(R.RESULT_DTYPE)
+
+
+def dump_outputs(path, recs):
+    """Write the records of one launch as path/<field>.npy, one array per
+    field of the 16-B record (mi_cls.h), every packet in batch order:
+    float64 for the 32-bit in_flags word, float32 for the 8- and 16-bit
+    fields (both exact).  1 M packets: 40 MB; of a larger batch a fixed,
+    seeded sample of DUMP_MAX_ROWS packets is written, with their indexes in
+    sample_index.npy (48 MB in all)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if recs.shape[0] > DUMP_MAX_ROWS:
+        idx = np.sort(np.random.default_rng(0).choice(recs.shape[0], DUMP_MAX_ROWS, replace=False))
+        np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+        recs = recs[idx]
+    for name in recs.dtype.names:
+        col = recs[name]
+        np.save(os.path.join(path, f"{name}.npy"),
+                col.astype(np.float64 if col.dtype.itemsize > 2 else np.float32))
 
 
 def oracle_parity(prog, batch, got, threads=16, pktin_opt=0):
@@ -676,9 +713,14 @@ def main():
     # with checksum options the kernel reads every frame byte
     bytes_launch = batch.header_bytes() if not a.pktin_opt else \
         int(batch.len.astype("int64").sum()) + 22 * batch.n
-    out = records(t_out, batch.n).copy()
+    full = a.full and not a.timed_only
+    out = None
+    if a.dump_outputs or (full and not a.no_parity):
+        out = records(t_out, batch.n).copy()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out)
     parity = None
-    if not a.no_parity and not a.timed_only:
+    if full and not a.no_parity:
         # every rank checks its own shard: all of its records bit-exact vs the oracle
         log("oracle parity")
         parity = oracle_parity(prog, batch, out, pktin_opt=a.pktin_opt)
@@ -735,7 +777,7 @@ def main():
         if parity is not None:
             # AND over every rank's shard (each checked against the oracle)
             line["parity_vs_oracle"] = parity
-        if world == 1 and not a.timed_only:
+        if world == 1 and full:
             if pmc:
                 line["issue"] = issue_roof(kms, pmc)
             w2, _, _ = time_device(c, batch, dev, a.steps, a.warmup, rotate=a.rotate, streams=2)

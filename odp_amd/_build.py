@@ -7,11 +7,11 @@
                          control plane (odp_cls_api.h) + runtime subset and
                          packet I/O (odp_rt.h), linked against libmi_cls.so
   odp_amd/libodph.so     gcc: the ODP helper subset (odp/helper/odph_api.h)
-  examples/_bin/odp_classifier
+  oracle/_ref/odp_classifier
                          the reference's example/classifier/odp_classifier.c,
-                         compiled UNCHANGED from /root/reference against these
-                         headers and libraries (only when the reference tree is
-                         present, i.e. in the build container; the binary travels)
+                         compiled UNCHANGED against these headers and libraries
+                         by oracle/Makefile (only where the reference tree is
+                         present; the binary travels, it is never committed)
 """
 from __future__ import annotations
 
@@ -155,26 +155,21 @@ def build_test_drivers(force: bool = False):
     return built
 
 
-REF_EXAMPLE = "/root/reference/example/classifier/odp_classifier.c"
-EX_BIN = os.path.join(ROOT, "examples", "_bin")
+EXAMPLE = os.path.join(ROOT, "oracle", "_ref", "odp_classifier")
 
 
 def build_example(force: bool = False):
     """Compile the reference's example/classifier source, unchanged, against
     this build's odp_api.h / odph_api.h and link it with libodp_cls.so +
     libodph.so (north-star acceptance: the example links and runs unchanged).
-    Skipped when the reference tree is absent (GPU box: the binary travels)."""
-    if not os.path.exists(REF_EXAMPLE):
-        return None
-    os.makedirs(EX_BIN, exist_ok=True)
-    out = os.path.join(EX_BIN, "odp_classifier")
-    libs = [os.path.join(PKG, "libodp_cls.so"), os.path.join(PKG, "libodph.so")]
-    if not force and not _stale(out, [REF_EXAMPLE] + libs):
-        return None
-    _run(["gcc", "-O2", "-std=gnu11", "-I", INC, "-o", out, REF_EXAMPLE, "-L", PKG,
-          "-lodph", "-lodp_cls", "-Wl,-rpath,$ORIGIN/" + os.path.relpath(PKG, EX_BIN),
-          "-lpthread"])
-    return out
+    The recipe is oracle/Makefile's ref-example target, the binary
+    oracle/_ref/odp_classifier (never committed).  Nothing is built where the
+    reference tree is absent: the binary built where it is present travels."""
+    before = os.path.getmtime(EXAMPLE) if os.path.exists(EXAMPLE) else None
+    _run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref-example"] +
+         (["-B"] if force else []))
+    after = os.path.getmtime(EXAMPLE) if os.path.exists(EXAMPLE) else None
+    return EXAMPLE if after != before else None
 
 
 if __name__ == "__main__":

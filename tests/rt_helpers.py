@@ -15,7 +15,7 @@ from odp_amd import rules as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(ROOT, "tests", "_bin", "rx_driver")
-EXAMPLE = os.path.join(ROOT, "examples", "_bin", "odp_classifier")
+EXAMPLE = os.path.join(ROOT, "oracle", "_ref", "odp_classifier")
 
 # input_flags bits the driver reconstructs from the odp_packet_has_*() calls
 # (bit 0 cls_mark is reported through odp_packet_cls_mark, bits 20/21/26 have

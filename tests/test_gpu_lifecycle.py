@@ -123,10 +123,10 @@ def test_spec_one_compile_at_a_time(built, gpu):
 
 
 def test_bench_extras_one_gpu(built, gpu):
-    """bench.py --gpus 1 with its extras (the path the driver runs; the
-    extras run in their own process): rc 0, one JSON line, every extra
-    parity-checked and naming its kernel instantiation."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2",
+    """bench.py --gpus 1 --full with its extras (the extras run in their own
+    process): rc 0, one JSON line, every extra parity-checked and naming its
+    kernel instantiation."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2",
                         "--warmup", "1", "--packets", "100000", "--no-cpu", "--no-runtime"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=400,
                        cwd=ROOT)
@@ -147,3 +147,33 @@ def test_bench_extras_one_gpu(built, gpu):
     # 8000-character stdout tail
     assert list(line)[-1] == "e2e"
     assert len(lines[0]) < 7500, len(lines[0])
+
+
+def test_bench_plain_run_dumps_outputs(built, gpu, tmp_path):
+    """A plain bench.py run times its steps and nothing else (no parity,
+    baseline, end-to-end or extra leg on the line), --steps sets the number
+    of timed steps, and --dump-outputs writes the last timed step's records,
+    one float array per record field: they equal the oracle's on the same
+    (seeded) workload.  steps = 3 ends on a device copy other than the first."""
+    n = 20_000
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
+                        "--warmup", "1", "--packets", str(n), "--dump-outputs", str(out)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120,
+                       cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1
+    assert line["ms_per_step"] > 0 and line["value"] > 0
+    assert abs(line["value"] - n / line["ms_per_step"] / 1e3) <= 0.02 * line["value"]
+    for leg in ("parity_vs_oracle", "pipelined", "e2e", "cpu_baseline", "extra"):
+        assert leg not in line, leg
+    b, prog = R.config3(n)
+    exp = oracle_run(prog, b)[0]
+    assert sorted(p.name for p in out.iterdir()) == sorted(f"{f}.npy" for f in exp.dtype.names)
+    for f in exp.dtype.names:
+        got = np.load(out / f"{f}.npy")
+        assert got.dtype in (np.float32, np.float64) and got.shape == (n,), f
+        assert np.array_equal(got, exp[f].astype(got.dtype)), f

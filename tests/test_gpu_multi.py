@@ -99,7 +99,7 @@ def test_bench_two_ranks_one_device(built, gpu):
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29533", os.path.join(H.ROOT, "bench.py"),
                         "--gpus", "2", "--steps", "3", "--warmup", "1", "--packets", "100000",
-                        "--config", "3"],
+                        "--config", "3", "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=240,
                        env=env, cwd=H.ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -12,7 +12,7 @@ if [ "$3" != "skip-tests" ]; then
     > $OUT/pytest.txt 2>&1 || { echo "pytest failed"; tail -30 $OUT/pytest.txt; exit 1; }
   tail -3 $OUT/pytest.txt
 fi
-timeout -k 10 400 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
 for c in $CFGS; do
   timeout -k 10 900 tools/profile.sh $TAG $c > $OUT/prof_c$c.log 2>&1 || { echo "profile $c failed"; cat $OUT/prof_c$c.log; exit 1; }
