@@ -321,6 +321,79 @@ int mi_cls_pktin_opt_set(mi_cls_ctx_t *ctx, uint64_t opt);
 int mi_cls_batch_hint(mi_cls_ctx_t *ctx, uint32_t max_batch);
 
 /* ------------------------------------------------------------------------
+ * pktout checksum insertion: the transmit half of the checksum offloads
+ * (reference pktio/loop.c:386-472 loopback_fix_checksums, odp_packet.c:
+ * 1888-2063 _odp_packet_{ipv4,udp,tcp,sctp}_chksum_insert).  Per packet the
+ * IPv4 header checksum, the UDP or TCP checksum, or the SCTP CRC-32C is
+ * computed and written into the frame.  Nothing is parsed: l3 / l4 are the
+ * packet's offsets as its metadata has them (0xFFFF: invalid).
+ *   IP version from frame[l3] >> 4: 4 with len - l3 >= 20 (protocol
+ *   frame[l3 + 9], 255 when MF or the fragment offset is set), 6 with
+ *   len - l3 >= 40 (next header frame[l3 + 6], no extension-header walk);
+ *   anything else: nothing is written.
+ *   A checksum is inserted when the packet is of its protocol and
+ *   (<l>_chksum_set ? <l>_chksum : the pktout_opt bit): IPv4 under the L3
+ *   pair, UDP (17) / TCP (6) / SCTP (132) under the L4 pair.  pktout_opt is
+ *   odp_pktout_config_opt_t.all_bits: bits 4-7 ipv4 / udp / tcp / sctp
+ *   _chksum (the _ena bits 0-3 are not consulted, as in loop.c).
+ *   IPv4: over the 4 IHL header bytes, stored at l3 + 10; not when IHL < 5
+ *   or the header ends past the frame.  UDP / TCP: pseudo header from the
+ *   addresses as stored, the protocol, and the UDP length field as stored
+ *   (TCP: len - l4), then [l4, len); UDP 0 is stored as 0xFFFF; UDP at
+ *   l4 + 6, TCP at l4 + 16 (the reference stores TCP at l4 + 6, odp_packet.c:
+ *   1988: a deviation).  SCTP: CRC-32C, init ~0, over [l4, len) with the
+ *   field zero, complemented, little-endian at l4 + 8.
+ *   Contract for the L4 checksums: l4 valid, l4 - l3 even and at least 20
+ *   (IPv4) / 40 (IPv6), the checksum field wholly inside the frame; a packet
+ *   that violates it is left unchanged for that protocol.  No byte outside
+ *   [off, off + len) is stored.  Two descriptors naming one frame: undefined.
+ * ---------------------------------------------------------------------- */
+typedef struct mi_cls_tx_desc {
+	uint16_t l3, l4;        /* offsets from the frame start, 0xFFFF invalid     */
+	uint8_t  flags;         /* MI_CLS_TXF_*                                     */
+	uint8_t  rsv[3];
+} mi_cls_tx_desc_t;     /* 8 B */
+
+#define MI_CLS_TXF_L3_SET 0x01u  /* l3_chksum_set: the L3 override is valid       */
+#define MI_CLS_TXF_L3     0x02u  /* l3_chksum: insert (1) / do not insert (0)     */
+#define MI_CLS_TXF_L4_SET 0x04u  /* l4_chksum_set                                 */
+#define MI_CLS_TXF_L4     0x08u  /* l4_chksum                                     */
+
+/* done[i]: the checksums written into packet i */
+#define MI_CLS_TX_IPV4 1u
+#define MI_CLS_TX_UDP  2u
+#define MI_CLS_TX_TCP  4u
+#define MI_CLS_TX_SCTP 8u
+
+/* Insert into n packets in device memory: the batch contract of
+ * mi_cls_classify (offsets, any alignment, the readable tail up to each
+ * frame's 16-B rounding); desc_dev 8-byte aligned; done_dev (n bytes) may be
+ * NULL.  The context needs no rules.  Stream-ordered on `stream`; returns
+ * after the launch is enqueued.  n == 0: 0.  No device: -ENODEV. */
+int mi_cls_chksum_insert(mi_cls_ctx_t *ctx, uint8_t *pkts_dev, const uint32_t *off_dev,
+			 const uint16_t *len_dev, const mi_cls_tx_desc_t *desc_dev, uint32_t n,
+			 uint64_t pktout_opt, uint8_t *done_dev, void *stream);
+
+/* Host-memory batch (the pktio send path): inserts into the n frames packed
+ * at pkts_host (every frame inside `bytes`) and waits.  When pkts_host,
+ * off_host, len_host, desc_host (and done_host, if given) are page-locked
+ * (mi_cls_host_alloc) and every frame's 16-B rounding lies inside `bytes`
+ * the kernel works on the frames in place; otherwise the batch goes through
+ * the context's staging buffers and the frames are copied back.  The submit
+ * form returns a ticket of the context's ring (mi_cls_classify_host_submit:
+ * 0 for n == 0, up to 8 batches in flight, buffers untouched until the
+ * wait). */
+int mi_cls_chksum_insert_host(mi_cls_ctx_t *ctx, uint8_t *pkts_host, size_t bytes,
+			      const uint32_t *off_host, const uint16_t *len_host,
+			      const mi_cls_tx_desc_t *desc_host, uint32_t n, uint64_t pktout_opt,
+			      uint8_t *done_host);
+int mi_cls_chksum_insert_host_submit(mi_cls_ctx_t *ctx, uint8_t *pkts_host, size_t bytes,
+				     const uint32_t *off_host, const uint16_t *len_host,
+				     const mi_cls_tx_desc_t *desc_host, uint32_t n, uint64_t pktout_opt,
+				     uint8_t *done_host, uint64_t *ticket);
+int mi_cls_chksum_insert_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
+
+/* ------------------------------------------------------------------------
  * Receive delivery on the GPU: the host steps of loopback_recv /
  * pcapif_recv_pkt after classification (pktio/loop.c:308-373, pcap.c:
  * 330-352) for packets whose headers and buffers are in page-locked host

@@ -318,6 +318,16 @@ struct mi_cls_dlv_args;
 int odp_amd_cls_deliver(odp_pktio_t pktio, const struct mi_cls_dlv_args *args, uint64_t *ticket);
 int odp_amd_cls_deliver_wait(odp_pktio_t pktio, uint64_t ticket);
 
+/* pktout checksum insertion of a send burst on the pktio's transmit context
+ * (mi_cls_chksum_insert_host; a pktio over several GPUs uses its first
+ * device); the context is created by the first call -- n == 0 does only
+ * that (odp_pktio_start).  Synchronous. */
+struct mi_cls_tx_desc;
+int odp_amd_cls_chksum_insert_host(odp_pktio_t pktio, uint8_t *pkts, size_t bytes,
+				   const uint32_t *off, const uint16_t *len,
+				   const struct mi_cls_tx_desc *desc, uint32_t n, uint64_t pktout_opt,
+				   uint8_t *done);
+
 /* Create the device context, upload the current rule snapshot and run a
  * warm-up launch (odp_pktio_start). */
 int odp_amd_cls_prepare(odp_pktio_t pktio, int parse_only);

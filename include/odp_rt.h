@@ -492,6 +492,14 @@ typedef enum {
 
 odp_packet_chksum_status_t odp_packet_l3_chksum_status(odp_packet_t pkt);
 odp_packet_chksum_status_t odp_packet_l4_chksum_status(odp_packet_t pkt);
+
+/* Per-packet override of the pktio's pktout checksum configuration
+ * (include/odp/api/spec/packet.h, packet_inlines.h:423-437): insert (1) or
+ * do not insert (0) the L3 (IPv4 header) / L4 (UDP, TCP, SCTP) checksum when
+ * the packet is sent.  Cleared by packet alloc and by the loop pktio's
+ * receive (packet_parse_reset(.., 1), loop.c:308). */
+void odp_packet_l3_chksum_insert(odp_packet_t pkt, int insert);
+void odp_packet_l4_chksum_insert(odp_packet_t pkt, int insert);
 int odp_packet_has_l2(odp_packet_t pkt);
 int odp_packet_has_l3(odp_packet_t pkt);
 int odp_packet_has_l4(odp_packet_t pkt);
@@ -892,6 +900,10 @@ uint64_t odp_pktio_to_u64(odp_pktio_t pktio);
 /* 1 when a pktio has no more input and no receive burst in flight (pcap past
  * EOF, loop queue empty), 0 otherwise, -1 on a bad handle. */
 int odp_amd_pktio_rx_idle(odp_pktio_t pktio);
+/* odp_pktout_send calls of a loop pktio that ran the pktout checksum kernel,
+ * and how many of them went through the bounce buffer (a packet outside the
+ * page-locked pools); 0, or -1 on a bad handle. */
+int odp_amd_pktio_tx_stats(odp_pktio_t pktio, uint64_t *bursts, uint64_t *bounced);
 
 #ifdef __cplusplus
 }

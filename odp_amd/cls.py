@@ -153,6 +153,11 @@ def _load():
         "mi_cls_classify": (i32, [vp, vp, vp, vp, u32, vp, vp]),
         "mi_cls_strerror": (C.c_char_p, [i32]),
         "mi_cls_program_info": (i32, [vp, C.c_size_t, C.POINTER(u32), u32]),
+        "mi_cls_chksum_insert": (i32, [vp, vp, vp, vp, vp, u32, C.c_uint64, vp, vp]),
+        "mi_cls_chksum_insert_host": (i32, [vp, vp, C.c_size_t, vp, vp, vp, u32, C.c_uint64, vp]),
+        "mi_cls_chksum_insert_host_submit": (i32, [vp, vp, C.c_size_t, vp, vp, vp, u32, C.c_uint64, vp,
+                                                   C.POINTER(C.c_uint64)]),
+        "mi_cls_chksum_insert_host_wait": (i32, [vp, C.c_uint64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -212,6 +217,84 @@ def lib():
 
 def _h(x):
     return x or 0
+
+
+# mi_cls_tx_desc_t (include/mi_cls.h): l3, l4, flags (bit 0 l3_chksum_set,
+# 1 l3_chksum, 2 l4_chksum_set, 3 l4_chksum)
+TX_DESC_DTYPE = np.dtype([("l3", "<u2"), ("l4", "<u2"), ("flags", "u1"), ("rsv", "u1", (3,))])
+
+
+class TxContext:
+    """A device context for pktout checksum insertion (mi_cls_chksum_insert
+    and its host entries); needs no rules."""
+
+    def __init__(self, gpu: int = 0):
+        self.L = lib()
+        ctx = C.c_void_p()
+        rc = self.L.mi_cls_ctx_create(gpu, C.byref(ctx))
+        if rc:
+            raise RuntimeError(f"mi_cls_ctx_create: {rc} ({self.L.mi_cls_strerror(rc).decode()})")
+        self.ctx = ctx
+
+    def close(self):
+        if self.ctx:
+            self.L.mi_cls_ctx_destroy(self.ctx)
+            self.ctx = None
+
+    def insert_device(self, d_buf, d_off, d_len, d_desc, n, opt, d_done=0, stream=0):
+        """On device pointers (ints), stream-ordered.  Returns the C status."""
+        return self.L.mi_cls_chksum_insert(self.ctx, d_buf, d_off, d_len, d_desc, n, int(opt),
+                                           d_done or None, stream or None)
+
+    def insert(self, batch, desc, opt, device="cuda:0"):
+        """Upload a pktgen.Batch and its descriptors (TX_DESC_DTYPE), insert
+        the checksums, return (buffer bytes, done bytes) as numpy arrays."""
+        import torch
+        dev = torch.device(device)
+        n = batch.n
+        desc = np.ascontiguousarray(desc, dtype=TX_DESC_DTYPE)
+        assert desc.shape[0] == n
+        t_buf = torch.from_numpy(np.ascontiguousarray(batch.buf)).to(dev)
+        t_off = torch.from_numpy(batch.off.astype(np.uint32).view(np.int32)).to(dev)
+        t_len = torch.from_numpy(batch.len.astype(np.uint16).view(np.int16)).to(dev)
+        t_desc = torch.from_numpy(desc.view(np.int64).copy() if n else np.zeros(1, np.int64)).to(dev)
+        t_done = torch.zeros(max(1, n), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.insert_device(t_buf.data_ptr(), t_off.data_ptr(), t_len.data_ptr(),
+                                t_desc.data_ptr(), n, opt, t_done.data_ptr(), stream)
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_chksum_insert: {rc} ({self.L.mi_cls_strerror(rc).decode()})")
+        torch.cuda.synchronize(dev)
+        return t_buf.cpu().numpy(), t_done.cpu().numpy()[:n]
+
+    def insert_host(self, buf, off, ln, desc, opt, done=None, submit=False):
+        """mi_cls_chksum_insert_host on numpy arrays (views of a PinnedArray
+        are worked on in place, other arrays go through the staging
+        buffers); buf is modified.  submit: the _submit / _wait pair."""
+        n = int(off.shape[0])
+        args = (self.ctx, buf.ctypes.data, buf.nbytes, off.ctypes.data, ln.ctypes.data,
+                desc.ctypes.data, n, int(opt), done.ctypes.data if done is not None else None)
+        if submit:
+            t = C.c_uint64()
+            rc = self.L.mi_cls_chksum_insert_host_submit(*args, C.byref(t))
+            if rc == 0:
+                rc = self.L.mi_cls_chksum_insert_host_wait(self.ctx, t.value)
+        else:
+            rc = self.L.mi_cls_chksum_insert_host(*args)
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_chksum_insert_host: {rc}")
+
+
+def chksum_insert(batch, desc, opt, gpu: int = 0):
+    """pktout checksum insertion of a pktgen.Batch on the GPU
+    (mi_cls_chksum_insert): desc is an array of TX_DESC_DTYPE (the packets'
+    l3 / l4 offsets and override flags), opt the
+    odp_pktout_config_opt_t.all_bits.  Returns (buffer bytes, done bytes)."""
+    c = TxContext(gpu)
+    try:
+        return c.insert(batch, desc, opt, device=f"cuda:{gpu}")
+    finally:
+        c.close()
 
 
 class Classifier:

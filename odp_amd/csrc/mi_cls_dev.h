@@ -791,6 +791,9 @@ __device__ __forceinline__ uint32_t nib_bytes(uint32_t nib)
 // yinv), plus the init's contribution ~0 x^(8 n), n = len - l4, = y1[n % 64]
 // z[n / 64].  One GF(2) multiply per block and two per frame.  Returns the
 // finished CRC for the asking lanes.
+// WIN0 = false (the transmit kernel, mi_cls_tx_dev.h: no staged window):
+// block 0 is read from memory like the others and `wb` is unused.
+template <bool WIN0 = true>
 __device__ __forceinline__ uint32_t sctp_crc_wave(__amdgpu_buffer_rsrc_t rs, const uint32_t *wb,
 						  uint32_t boff, uint32_t l4, uint32_t len, uint32_t ask,
 						  uint32_t lane, const uint32_t *tab)
@@ -824,10 +827,10 @@ __device__ __forceinline__ uint32_t sctp_crc_wave(__amdgpu_buffer_rsrc_t rs, con
 		for (uint32_t i = 0; i < 4; ++i) {
 			const uint32_t o = o0 + 16u * i;
 			v[i] = __builtin_amdgcn_raw_buffer_load_b128(
-				rs, (live && b != 0u && o < flen && o + 16u > fl4) ? ob0 + o : OOB_OFF, 0, 0);
+				rs, (live && (!WIN0 || b != 0u) && o < flen && o + 16u > fl4) ? ob0 + o : OOB_OFF, 0, 0);
 		}
 		__builtin_amdgcn_s_setprio(0);
-		if (__ballot(live && b == 0u) != 0ull) {
+		if (WIN0 && __ballot(live && b == 0u) != 0ull) {
 			// block 0: the owner's staged window
 			const uint32_t *w = wb + (live && b == 0u ? lo : lane);
 #pragma unroll
@@ -2953,6 +2956,20 @@ int mi_cls_launch_rx_chain(hipStream_t st, const mi_cls_rxc_args_t &a, const mi_
 // loop receive staging on the device (mi_cls_rxc_args_t.stage)
 int mi_cls_launch_rx_stage(hipStream_t st, const mi_cls_rxc_args_t &a, const mi_cls_rxdev_t &d, uint64_t bytes,
 			   bool preload);
+
+// pktout checksum insertion (mi_cls_chksum_insert; kernel: mi_cls_tx_dev.h,
+// mi_cls_kt.hip).  grid == 0: preload only.
+struct TxArgs {
+	uint8_t *pkts;
+	const uint32_t *off;
+	const uint16_t *len;
+	const mi_cls_tx_desc_t *desc;
+	uint8_t *done;          // may be null
+	uint32_t n;
+	uint32_t opt;           // odp_pktout_config_opt_t.all_bits
+};
+#define TX_NW 4             // waves per block
+int mi_cls_launch_tx(unsigned grid, hipStream_t st, const TxArgs &a);
 
 // Every launcher goes through mi_launch.  grid == 0 launches nothing: it
 // resolves the instantiation on the current device (hipFuncGetAttributes

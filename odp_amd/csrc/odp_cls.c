@@ -89,6 +89,9 @@ typedef struct {
 	uint32_t headroom;
 	mi_cls_ctx_t *ctx;       /* device 0 of the pktio (the group's first context) */
 	mi_cls_ctx_t *pctx;      /* parse-only context (empty table) */
+	mi_cls_ctx_t *tctx;      /* transmit context (pktout checksum insertion): its
+				  * own stream and ticket ring, so a sender never
+				  * shares them with a receive burst in flight */
 	/* multi-GPU receive (odp_amd_cls_pktio_create_multi): host bursts are
 	 * sharded over these devices (mi_cls_group_classify_host) */
 	mi_cls_group_t *grp;
@@ -795,6 +798,8 @@ int odp_amd_cls_pktio_destroy(odp_pktio_t h)
 		mi_cls_ctx_destroy(e->ctx);
 	if (e->pctx)
 		mi_cls_ctx_destroy(e->pctx);
+	if (e->tctx)
+		mi_cls_ctx_destroy(e->tctx);
 	free(e->blob);
 	memset(e, 0, sizeof(*e));
 	return 0;
@@ -1618,6 +1623,27 @@ int odp_amd_cls_classify_host_wait(odp_pktio_t h, uint64_t ticket)
 	if (e->grp)
 		return mi_cls_group_classify_host_wait(e->grp, ticket);
 	return e->ctx ? mi_cls_classify_host_wait(e->ctx, ticket) : -EINVAL;
+}
+
+/* pktout checksum insertion of a send burst (mi_cls_chksum_insert_host) on
+ * the pktio's transmit context, created by the first call on the pktio's
+ * device (its first one when it spans several); n == 0 only creates it
+ * (odp_pktio_start).  Returns when the checksums are in the frames. */
+int odp_amd_cls_chksum_insert_host(odp_pktio_t h, uint8_t *pkts, size_t bytes, const uint32_t *off,
+				   const uint16_t *len, const mi_cls_tx_desc_t *desc, uint32_t n,
+				   uint64_t pktout_opt, uint8_t *done)
+{
+	pktio_t *e = get_pktio(h);
+
+	if (!e)
+		return -EINVAL;
+	if (!e->tctx) {
+		int rc = mi_cls_ctx_create(e->ngpu > 1 ? e->gpus[0] : e->gpu, &e->tctx);
+
+		if (rc)
+			return rc;
+	}
+	return mi_cls_chksum_insert_host(e->tctx, pkts, bytes, off, len, desc, n, pktout_opt, done);
 }
 
 /* GPU receive delivery of a classified burst (mi_cls_deliver_submit) on the

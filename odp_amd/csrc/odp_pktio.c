@@ -177,6 +177,21 @@ typedef struct {
 	uint64_t rxtab_gen;
 	odp_pool_t rx_pools[MI_CLS_RX_POOLS];
 	uint32_t rx_np, rx_want[MI_CLS_RX_POOLS];
+	/* transmit (pktout checksum insertion): a send burst's descriptors in
+	 * page-locked memory, and the bounce buffer of bursts with a packet
+	 * outside the page-locked arena (pageable pools) */
+	pthread_mutex_t txl;    /* held across the kernel's launch and wait */
+	uint8_t *tx_arr;        /* one allocation: tx_desc, tx_off, tx_len (tx_cap each) */
+	mi_cls_tx_desc_t *tx_desc;
+	uint32_t *tx_off;
+	uint16_t *tx_len;
+	uint32_t tx_cap;
+	int tx_pinned;
+	uint64_t tx_bursts, tx_bounced;   /* send calls that ran the kernel / of them
+					   * through the bounce buffer */
+	uint8_t *tx_stage;
+	size_t tx_stage_cap;
+	int tx_stage_pinned;
 	uint64_t prof[16];      /* ODP_AMD_RX_PROF: ns staging / classifying / delivering, bursts,
 				 * then of delivering: ns preparing / enqueueing, TSC ticks in
 				 * packet allocation / frame copies; GPU delivery: ns deciding +
@@ -186,6 +201,7 @@ typedef struct {
 } rt_pktio_t;
 
 static void rx_sets_free(rt_pktio_t *e);
+static void tx_free(rt_pktio_t *e);
 static void fbuf_free(rt_pktio_t *e);
 static int rx_finish(rt_pktio_t *e, rx_set_t *s, odp_packet_t out[], int max_out);
 static int rx_dlv_end(rt_pktio_t *e, rx_set_t *s, odp_packet_t out[], int max_out);
@@ -585,6 +601,7 @@ odp_pktio_t odp_pktio_open(const char *name, odp_pool_t pool, const odp_pktio_pa
 	e->param = *param;
 	odp_pktio_config_init(&e->config);
 	odp_spinlock_init(&e->rxl);
+	pthread_mutex_init(&e->txl, NULL);
 	e->state = ST_OPENED;
 	e->promisc = 1;
 	if (drv == DRV_PCAP && pcap_open(e, name)) {
@@ -635,6 +652,9 @@ int odp_pktio_capability(odp_pktio_t h, odp_pktio_capability_t *c)
 	odp_pktio_config_init(&c->config);
 	c->config.parser.layer = ODP_PROTO_LAYER_ALL;
 	c->config.pktin.all_bits = RT_PKTIN_OPT_MASK;
+	/* loop.c:694-715: checksum insertion (and the per-packet override
+	 * enables) on the loop pktio; the pcap driver has no such offload */
+	c->config.pktout.all_bits = e->drv == DRV_LOOP ? RT_PKTOUT_OPT_MASK : 0;
 	c->config.enable_loop = 0;
 	c->set_op.op.promisc_mode = e->drv == DRV_PCAP;
 	c->maxlen.equal = 1;
@@ -656,8 +676,10 @@ int odp_pktio_config(odp_pktio_t h, const odp_pktio_config_t *config)
 		config = &def;
 	}
 	/* parser options, pktin checksum validation and drop-on-error options
-	 * (bits 2-10); no timestamps, pktout offloads, IPsec or LSO */
-	if ((config->pktin.all_bits & ~RT_PKTIN_OPT_MASK) || config->pktout.all_bits ||
+	 * (bits 2-10), pktout checksum insertion on a loop pktio (bits 0-7); no
+	 * timestamps, other pktout offloads, IPsec or LSO */
+	if ((config->pktin.all_bits & ~RT_PKTIN_OPT_MASK) ||
+	    (config->pktout.all_bits & ~(e->drv == DRV_LOOP ? RT_PKTOUT_OPT_MASK : 0ull)) ||
 	    config->enable_loop || config->inbound_ipsec || config->outbound_ipsec ||
 	    config->enable_lso) {
 		RT_ERR("pktio %s: unsupported configuration option\n", e->name);
@@ -824,6 +846,17 @@ int odp_pktio_start(odp_pktio_t h)
 				(void)odp_amd_cls_spec_wait(h);
 		}
 	}
+	/* pktout checksum insertion configured: its GPU context before traffic,
+	 * also when the input side needs none */
+	if (e->drv == DRV_LOOP && (e->config.pktout.all_bits & RT_PKTOUT_OPT_MASK)) {
+		int rc = odp_amd_cls_chksum_insert_host(h, NULL, 0, NULL, NULL, NULL, 0, 0, NULL);
+
+		if (rc) {
+			RT_ERR("pktio %s: GPU transmit path unavailable (%s)\n", e->name,
+			       mi_cls_strerror(rc));
+			return -1;
+		}
+	}
 	e->state = ST_STARTED;
 	if (e->param.in_mode == ODP_PKTIN_MODE_SCHED) {
 		odp_spinlock_lock(&pk_lock);
@@ -918,6 +951,7 @@ int odp_pktio_close(odp_pktio_t h)
 	free(e->foff);
 	free(e->flen);
 	rx_sets_free(e);
+	tx_free(e);
 	odp_spinlock_lock(&pk_lock);
 	memset(e, 0, sizeof(*e));
 	odp_spinlock_unlock(&pk_lock);
@@ -1565,6 +1599,10 @@ static void rx_prepare_each(rt_pktio_t *e, rx_set_t *s, int lo, int hi, rx_cnt_t
 			h->in_flags = 0;
 			h->err = 0;
 		}
+		/* packet_parse_reset(.., 1) (loop.c:308): a received packet carries
+		 * no pktout checksum overrides (the GPU deliveries write the whole
+		 * metadata block, this field as 0) */
+		h->tx_ck = 0;
 		h->input = e->hdl;
 		if (!h->err) {
 			c->octets += len;
@@ -3119,6 +3157,126 @@ int odp_pktin_recv_tmo(odp_pktin_queue_t q, odp_packet_t pkts[], int num, uint64
 }
 
 /* ============================================================ transmit */
+static void tx_free(rt_pktio_t *e)
+{
+	hmem_free(e->tx_arr, e->tx_pinned);
+	hmem_free(e->tx_stage, e->tx_stage_pinned);
+	pthread_mutex_destroy(&e->txl);
+	e->tx_arr = NULL;
+	e->tx_off = NULL;
+	e->tx_len = NULL;
+	e->tx_desc = NULL;
+	e->tx_stage = NULL;
+	e->tx_cap = 0;
+	e->tx_stage_cap = 0;
+}
+
+/* pktout checksum insertion of a send burst on a loop pktio
+ * (loopback_fix_checksums for every packet, pktio/loop.c:422-472, 581) on the
+ * GPU: nothing when no default is configured and no packet carries an
+ * override that asks for a checksum (no GPU call).  Otherwise the packets'
+ * descriptors are built in page-locked memory -- the data address relative to
+ * the page-locked arena, as the receive chain's, the length, the l3 / l4
+ * offsets and the override bits of the header -- and the kernel works on the
+ * frames in place; a burst with a packet outside the arena (pageable pools)
+ * goes through a page-locked bounce buffer.  Waits for the kernel.  The
+ * packets' override bits stay as they are (a packet the loop queue does not
+ * take goes back to the application with them): the loop receive resets them
+ * (packet_parse_reset(.., 1), loop.c:308).  0, or -1. */
+static int tx_chksum(rt_pktio_t *e, const odp_packet_t pkts[], int num)
+{
+	const uint64_t opt = e->config.pktout.all_bits & RT_PKTOUT_OPT_MASK;
+	int want = (opt & 0xF0u) != 0;
+
+	for (int i = 0; !want && i < num; i++) {
+		const uint32_t f = rt_pkt_hdr(pkts[i])->tx_ck;
+
+		want |= (f & (MI_CLS_TXF_L3_SET | MI_CLS_TXF_L3)) == (MI_CLS_TXF_L3_SET | MI_CLS_TXF_L3) ||
+			(f & (MI_CLS_TXF_L4_SET | MI_CLS_TXF_L4)) == (MI_CLS_TXF_L4_SET | MI_CLS_TXF_L4);
+	}
+	if (!want)
+		return 0;
+	const uint32_t n = (uint32_t)num;
+	int rc = -1;
+
+	pthread_mutex_lock(&e->txl);
+	if (n > e->tx_cap) {
+		const size_t cap = n < 4096u ? 4096u : (size_t)n + n / 2;
+
+		hmem_free(e->tx_arr, e->tx_pinned);
+		e->tx_cap = 0;
+		e->tx_arr = hmem_alloc(cap * (sizeof(mi_cls_tx_desc_t) + sizeof(uint32_t) + sizeof(uint16_t)),
+				       &e->tx_pinned);
+		if (!e->tx_arr)
+			goto out;
+		e->tx_desc = (mi_cls_tx_desc_t *)(void *)e->tx_arr;
+		e->tx_off = (uint32_t *)(void *)(e->tx_desc + cap);
+		e->tx_len = (uint16_t *)(void *)(e->tx_off + cap);
+		e->tx_cap = (uint32_t)cap;
+	}
+	uint8_t *lo = NULL, *base;
+	size_t span = 0, bytes = 0;
+	int in_place = e->tx_pinned && rt_pinned_arena(&lo, &span) && span < OOB_SPAN;
+
+	for (uint32_t i = 0; i < n; i++) {
+		const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
+		const uint8_t *d = h->head + h->data_off;
+		const uint32_t l = h->len > 65535 ? 65535 : h->len;
+		const rt_pool_t *rp = rt_pool((odp_pool_t)(uintptr_t)(h->ev.pool + 1u));
+
+		e->tx_len[i] = (uint16_t)l;
+		e->tx_desc[i] = (mi_cls_tx_desc_t){ .l3 = h->l3, .l4 = h->l4, .flags = (uint8_t)(h->tx_ck & 0xFu) };
+		if (in_place && rp && rp->pinned && d >= lo && (size_t)(d - lo) + l + 16u <= span)
+			e->tx_off[i] = (uint32_t)(d - lo);
+		else
+			in_place = 0;
+		bytes += (l + 63u) & ~63u;
+	}
+	if (in_place) {
+		base = lo;
+		bytes = span;
+	} else {
+		bytes += 64;
+		if (bytes >= OOB_SPAN)
+			goto out;
+		if (bytes > e->tx_stage_cap) {
+			hmem_free(e->tx_stage, e->tx_stage_pinned);
+			e->tx_stage_cap = 0;
+			e->tx_stage = hmem_alloc(bytes + bytes / 2, &e->tx_stage_pinned);
+			if (!e->tx_stage)
+				goto out;
+			e->tx_stage_cap = bytes + bytes / 2;
+		}
+		size_t off = 0;
+
+		for (uint32_t i = 0; i < n; i++) {
+			const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
+
+			memcpy(e->tx_stage + off, h->head + h->data_off, e->tx_len[i]);
+			e->tx_off[i] = (uint32_t)off;
+			off += (e->tx_len[i] + 63u) & ~63u;
+		}
+		base = e->tx_stage;
+	}
+	rc = odp_amd_cls_chksum_insert_host(e->hdl, base, bytes, e->tx_off, e->tx_len, e->tx_desc, n, opt,
+					    NULL);
+	if (rc) {
+		RT_ERR("pktio %s: pktout checksum insertion failed (%s)\n", e->name, mi_cls_strerror(rc));
+		rc = -1;
+		goto out;
+	}
+	for (uint32_t i = 0; !in_place && i < n; i++) {
+		pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
+
+		memcpy(h->head + h->data_off, e->tx_stage + e->tx_off[i], e->tx_len[i]);
+	}
+	e->tx_bursts++;
+	e->tx_bounced += !in_place;
+out:
+	pthread_mutex_unlock(&e->txl);
+	return rc;
+}
+
 int odp_pktout_send(odp_pktout_queue_t q, const odp_packet_t pkts[], int num)
 {
 	rt_pktio_t *e = get_pk(q.pktio);
@@ -3126,6 +3284,8 @@ int odp_pktout_send(odp_pktout_queue_t q, const odp_packet_t pkts[], int num)
 	if (!e || num < 0)
 		return -1;
 	if (e->state != ST_STARTED)
+		return -1;
+	if (e->drv == DRV_LOOP && num > 0 && tx_chksum(e, pkts, num))
 		return -1;
 	uint64_t octets = 0;
 
@@ -3257,6 +3417,21 @@ void odp_pktio_print(odp_pktio_t h)
 	       e->drv == DRV_PCAP ? "pcap" : e->drv == DRV_LOOP ? "loop" : "null",
 	       e->cls_enabled ? "enabled (GPU)" : "disabled", e->nframes, s.in_packets,
 	       s.in_errors, s.in_discards);
+}
+
+/* Build extension: send calls of the pktio that ran the pktout checksum
+ * kernel, and how many of them went through the bounce buffer. */
+int odp_amd_pktio_tx_stats(odp_pktio_t h, uint64_t *bursts, uint64_t *bounced)
+{
+	rt_pktio_t *e = get_pk(h);
+
+	if (!e || !bursts || !bounced)
+		return -1;
+	pthread_mutex_lock(&e->txl);
+	*bursts = e->tx_bursts;
+	*bounced = e->tx_bounced;
+	pthread_mutex_unlock(&e->txl);
+	return 0;
 }
 
 /* Build extension: 1 when the driver has no more input and no receive burst

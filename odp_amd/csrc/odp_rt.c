@@ -954,6 +954,7 @@ static void pkt_init(pkt_hdr_t *h, uint32_t len)
 	h->l2 = 0;   /* odp_packet_alloc sets l2 = 0 (packet.c packet_init) */
 	h->l3 = ODP_PACKET_OFFSET_INVALID;
 	h->l4 = ODP_PACKET_OFFSET_INVALID;
+	h->tx_ck = 0;
 	h->dst_queue = ODP_QUEUE_INVALID;
 	h->input = ODP_PKTIO_INVALID;
 	h->user_ptr = NULL;
@@ -1281,6 +1282,23 @@ odp_packet_chksum_status_t odp_packet_l4_chksum_status(odp_packet_t pkt)
 	if (!((h->in_flags >> 31) & 1u))
 		return ODP_PACKET_CHKSUM_UNKNOWN;
 	return (h->err & 0x40) ? ODP_PACKET_CHKSUM_BAD : ODP_PACKET_CHKSUM_OK;
+}
+
+/* packet_inlines.h:423-437 */
+void odp_packet_l3_chksum_insert(odp_packet_t pkt, int insert)
+{
+	pkt_hdr_t *h = rt_pkt_hdr(pkt);
+
+	h->tx_ck = (uint16_t)((h->tx_ck & ~(MI_CLS_TXF_L3_SET | MI_CLS_TXF_L3)) | MI_CLS_TXF_L3_SET |
+			      (insert ? MI_CLS_TXF_L3 : 0u));
+}
+
+void odp_packet_l4_chksum_insert(odp_packet_t pkt, int insert)
+{
+	pkt_hdr_t *h = rt_pkt_hdr(pkt);
+
+	h->tx_ck = (uint16_t)((h->tx_ck & ~(MI_CLS_TXF_L4_SET | MI_CLS_TXF_L4)) | MI_CLS_TXF_L4_SET |
+			      (insert ? MI_CLS_TXF_L4 : 0u));
 }
 
 /* accessor for odp_cls_hash_result (odp_cls.c) */

@@ -19,6 +19,9 @@
 /* odp_pktin_config_opt_t bits the receive path implements: ipv4/udp/tcp/
  * sctp checksum validation and the five drop-on-error options */
 #define RT_PKTIN_OPT_MASK 0x7FCull
+/* odp_pktout_config_opt_t bits a loop pktio implements: the four checksum
+ * insertion defaults (bits 4-7) and their per-packet override enables (0-3) */
+#define RT_PKTOUT_OPT_MASK 0xFFull
 #define RT_PKT_HEADROOM 128
 #define RT_PKT_TAILROOM 64
 
@@ -56,7 +59,10 @@ typedef struct pkt_hdr {
 			uint8_t cos;            /* CoS index, 0xff none */
 			uint16_t cls_mark;
 			uint16_t l2, l3, l4;
-			uint16_t rsv0;
+			/* pktout checksum overrides (MI_CLS_TXF_*: l3/l4_chksum_set,
+			 * l3/l4_chksum of packet_parser_t.flags); the GPU receive
+			 * delivery writes the block whole, this field as 0 */
+			uint16_t tx_ck;
 			uint32_t rsv1;
 			odp_queue_t dst_queue;
 			odp_pktio_t input;
