@@ -1,6 +1,11 @@
 """Native build of the MI355X classification path (in-tree, no JIT cache).
 
   odp_amd/libmi_cls.so   hipcc --offload-arch=gfx950: HIP kernels + mi_cls.h C ABI
+                         (mi_cls.hip, one unit per block shape), linked with
+                         two g++ units: the rule-program assembler
+                         (mi_cls_asm.cpp, host-only C++17, no HIP) and the
+                         specialised kernels' compile manager (mi_cls_spec.cpp,
+                         host C++ over the HIP module API)
   odp_amd/mi_cls_jitc    g++ over hipRTC: compiles program-specialised kernels,
                          started by libmi_cls.so as a child process
   odp_amd/libodp_cls.so  gcc: the ODP library of this build -- classification
@@ -60,11 +65,17 @@ def build(force: bool = False, out_dir: str = PKG, defines=(), src_dir: str = SR
                       os.path.join(SRC, "odp_rt_internal.h")]
     built = []
     mi_hdr = os.path.join(SRC, "mi_cls_dev.h")
+    prog_hdr = os.path.join(SRC, "mi_cls_prog.h")
+    # host-only units of libmi_cls.so (g++): the assembler, the compile manager
+    asm_src = os.path.join(SRC, "mi_cls_asm.cpp")
+    spec_src = os.path.join(SRC, "mi_cls_spec.cpp")
+    host_deps = [asm_src, spec_src, prog_hdr, os.path.join(SRC, "mi_cls_asm.h"),
+                 os.path.join(SRC, "mi_cls_spec.h")]
     k_srcs = [os.path.join(SRC, f"mi_cls_k{w}.hip") for w in (4, 8, 12, 16, "f", "f12", "f16", "c4",
                                                               "c16", "d", "t")]
     tx_hdr = os.path.join(SRC, "mi_cls_tx_dev.h")
     variant = bool(defines) or src_dir != globals()["SRC"]
-    if force or variant or _stale(mi_so, [mi_src, mi_hdr, tx_hdr] + k_srcs + hdrs + [__file__]):
+    if force or variant or _stale(mi_so, [mi_src, mi_hdr, tx_hdr] + host_deps + k_srcs + hdrs + [__file__]):
         # one translation unit per block shape + the host code, compiled in
         # parallel (the kernel instantiations dominate the build time)
         import concurrent.futures as cf
@@ -85,13 +96,18 @@ def build(force: bool = False, out_dir: str = PKG, defines=(), src_dir: str = SR
             stub = ["-DMI_CLS_STUB"] if keep and src != mi_src and \
                 os.path.basename(src) not in keep else []
             jobs.append([HIPCC] + flags + stub + ["-c", "-o", obj, src])
+        host = ["g++", "-O2", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-I", INC, "-I", SRC, "-I", tmp]
+        for src, extra in ((asm_src, []), (spec_src, ["-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include"])):
+            obj = os.path.join(tmp, os.path.basename(src) + ".o")
+            objs.append(obj)
+            jobs.append(host + extra + ["-c", "-o", obj, src])
         with cf.ThreadPoolExecutor(max_workers=len(jobs)) as ex:
             list(ex.map(_run, jobs))
         _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", mi_so] + objs)
         shutil.rmtree(tmp, ignore_errors=True)
         built.append(mi_so)
     # the program-specialised kernels' compiler, run as a child process of
-    # libmi_cls.so (mi_cls.hip spec_compile): host code over hipRTC
+    # libmi_cls.so (mi_cls_spec.cpp spec_compile): host code over hipRTC
     jitc_src = os.path.join(SRC, "mi_cls_jitc.cpp")
     jitc = os.path.join(out_dir, "mi_cls_jitc")
     if force or _stale(jitc, [jitc_src]):
@@ -117,18 +133,20 @@ def build(force: bool = False, out_dir: str = PKG, defines=(), src_dir: str = SR
 
 def write_src_inc(path, defines=(), src_dir=SRC):
     """The kernel sources as C string literals for hipRTC (program-specialised
-    kernels, mi_cls.hip): mi_cls.h, mi_cls_dev.h and the build's -D options,
+    kernels, mi_cls_spec.cpp): mi_cls.h, mi_cls_prog.h, mi_cls_dev.h and the build's -D options,
     so a specialised kernel is compiled from exactly the code of this build."""
     def lit(name, text):
         assert ")MICLS\"" not in text
         return f'static const char {name}[] = R"MICLS({text})MICLS";\n'
     with open(os.path.join(INC, "mi_cls.h")) as f:
         h = f.read()
+    with open(os.path.join(src_dir, "mi_cls_prog.h")) as f:
+        prog = f.read()
     with open(os.path.join(src_dir, "mi_cls_dev.h")) as f:
         dev = f.read()
     defs = ", ".join(f'"-D{d}"' for d in defines)
     with open(path, "w") as f:
-        f.write(lit("mi_cls_src_h", h) + lit("mi_cls_src_dev", dev) +
+        f.write(lit("mi_cls_src_h", h) + lit("mi_cls_src_prog", prog) + lit("mi_cls_src_dev", dev) +
                 f"static const char *const mi_cls_src_defs[] = {{ {defs}{', ' if defs else ''}nullptr }};\n"
                 f'static const char mi_cls_src_arch[] = "{ARCH}";\n')
 

@@ -1,12 +1,12 @@
 // mi_cls_jitc: compiles one program-specialised classification kernel with
-// hipRTC in a process of its own (libmi_cls.so starts it, mi_cls.hip
+// hipRTC in a process of its own (libmi_cls.so starts it, mi_cls_spec.cpp
 // spec_compile).  Compiling in the library's own process left a compiler
 // thread running when a short-lived process exited, and the exit-time
 // teardown could deadlock with it; a child process holds nothing the parent
 // tears down, and the parent kills it at exit instead of waiting.
 //
-// Protocol (stdin): four length-prefixed sections, each "<bytes>\n" then the
-// bytes -- the kernel source, mi_cls.h, mi_cls_dev.h, and the name
+// Protocol (stdin): five length-prefixed sections, each "<bytes>\n" then the
+// bytes -- the kernel source, mi_cls.h, mi_cls_prog.h, mi_cls_dev.h, and the name
 // expression of the kernel instantiation; argv[1..] are the compile options.
 // stdout on success: "OK <lowered-name-bytes> <code-bytes>\n", the lowered
 // name, the code object.  On failure: "ERR <log-bytes>\n" and the log.
@@ -29,14 +29,14 @@ static bool read_section(std::string &out)
 
 int main(int argc, char **argv)
 {
-	std::string src, h, dev, name;
-	if (!read_section(src) || !read_section(h) || !read_section(dev) || !read_section(name))
+	std::string src, h, prog, dev, name;
+	if (!read_section(src) || !read_section(h) || !read_section(prog) || !read_section(dev) || !read_section(name))
 		return 2;
-	const char *hdrs[2] = { h.c_str(), dev.c_str() };
-	const char *names[2] = { "mi_cls.h", "mi_cls_dev.h" };
+	const char *hdrs[3] = { h.c_str(), prog.c_str(), dev.c_str() };
+	const char *names[3] = { "mi_cls.h", "mi_cls_prog.h", "mi_cls_dev.h" };
 	std::string log;
 	hiprtcProgram p;
-	if (hiprtcCreateProgram(&p, src.c_str(), "mi_cls_spec.hip", 2, hdrs, names) != HIPRTC_SUCCESS) {
+	if (hiprtcCreateProgram(&p, src.c_str(), "mi_cls_spec.hip", 3, hdrs, names) != HIPRTC_SUCCESS) {
 		printf("ERR 0\n");
 		return 0;
 	}

@@ -319,3 +319,32 @@ def test_joint_groups_host(built):
     assert with_joint["tree"] and with_joint["direct"] == without["direct"]
     assert with_joint["joint_direct"] == 128 and with_joint["joint_bitmap"] == 16, with_joint
     assert without["joint_direct"] == 0 and without["joint_bitmap"] == 0, without
+
+
+def test_no_portmerge_knob_is_read_per_load(built):
+    """MI_CLS_NO_PORTMERGE takes effect at every load, like the other
+    assembler knobs (it used to be read once per process): three UDP and
+    three TCP destination-port rules are one merged key class (a direct
+    block) by default, two classes (a bitmap block) with the knob set, and
+    one class again once it is unset -- all in one process."""
+    prog = [R.cos("d", queue=1)] + [R.cos(f"q{i}", queue=2 + i) for i in range(6)] + [("default", 0)]
+    for i in range(6):
+        term = R.PMR_UDP_DPORT if i < 3 else R.PMR_TCP_DPORT
+        prog.append(("pmr", [R.t_be16(term, 1000 + i)], 0, 1 + i, 0))
+    c = cls.Classifier(gpu=0)
+    try:
+        c.apply(prog)
+        assert "MI_CLS_NO_PORTMERGE" not in os.environ
+        merged = c.program_info()
+        os.environ["MI_CLS_NO_PORTMERGE"] = "1"
+        try:
+            split = c.program_info()
+        finally:
+            del os.environ["MI_CLS_NO_PORTMERGE"]
+        again = c.program_info()
+    finally:
+        c.close()
+    assert (merged["direct"], merged["bitmap"]) == (1, 0), merged
+    assert (split["direct"], split["bitmap"]) == (0, 1), split
+    assert split["words"] != merged["words"]
+    assert again == merged
