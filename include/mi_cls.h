@@ -446,6 +446,14 @@ typedef struct mi_cls_dlv {
 /* Entries one delivery groups at most: a burst with more entries must give
  * every entry qid 0xFF (mi_cls_deliver_submit rejects it otherwise). */
 #define MI_CLS_DLV_GROUP_MAX 8192
+/* An entry index, a group's count and a frame's rank each travel in 16 bits:
+ * gcnt bits 0-15, the rank in dec bits 16-31, the kernels' 16-bit LDS arrays
+ * (s_perm / s_rank in mi_cls_kd.hip). */
+#ifdef __cplusplus
+static_assert(MI_CLS_DLV_GROUP_MAX <= 0xFFFF, "a burst's indexes, counts and ranks fit 16 bits");
+#else
+_Static_assert(MI_CLS_DLV_GROUP_MAX <= 0xFFFF, "a burst's indexes, counts and ranks fit 16 bits");
+#endif
 
 typedef struct mi_cls_dlv_args {
 	const uint8_t *base;    /* the classified batch's base (host VA)           */
@@ -547,8 +555,10 @@ typedef struct mi_cls_rxc_args {
 	uint64_t *ent;                /* per frame: the delivered packet (0: none)  */
 	uint32_t *perm;               /* frames grouped by queue group (stable)     */
 	uint32_t *gcnt;               /* MI_CLS_DLV_GROUPS: the group's frame count in
-				       * bits 0-15; bit 24 set when they all have one
-				       * CoS, its index in bits 16-23              */
+				       * bits 0-15 (MI_CLS_DLV_GROUP_MAX <= 0xFFFF); bit
+				       * 24 set when they all have one CoS, its index
+				       * in bits 16-23 (mi_cls_result_t.cos is 8 bits:
+				       * the 256 CoS of mi_cls_rxtab_t.cos_pool)   */
 	mi_cls_rx_out_t *out;
 } mi_cls_rxc_args_t;
 

@@ -283,6 +283,13 @@ __device__ __forceinline__ unsigned long long match_lanes(uint32_t v, int bits)
 static_assert(RXD_PER * RXD_THREADS == MI_CLS_DLV_GROUP_MAX, "one block holds a burst");
 static_assert(RXD_WAVES == MI_CLS_RX_POOLS, "one wave per pool slot");
 static_assert(RXD_WAVES * 4 == MI_CLS_DLV_GROUPS, "four queue groups per wave");
+// the packing of the outputs: a group's count in gcnt bits 0-15, a frame's
+// index in the uint16_t s_perm, its rank in the uint16_t s_rank and in dec
+// bits 16-31 all hold values up to MI_CLS_DLV_GROUP_MAX; gcnt bits 16-23 hold
+// a CoS index, 8 bits as in the record, one per entry of the table's cos_pool
+static_assert(MI_CLS_DLV_GROUP_MAX <= 0xFFFF, "counts, indexes and ranks of a burst fit 16 bits");
+static_assert(sizeof(mi_cls_result_t::cos) == 1 && sizeof(mi_cls_rxtab_t::cos_pool) == 256,
+	      "a CoS index fits the 8 bits of gcnt bits 16-23: 256 CoS at most");
 __global__ __launch_bounds__(RXD_THREADS) void mi_cls_rx_decide_kernel(mi_cls_rxc_args_t a, mi_cls_rxdev_t d)
 {
 	__shared__ uint8_t s_k[MI_CLS_DLV_GROUP_MAX];        // fresh frame: its slot, else 0xFF
