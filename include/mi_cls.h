@@ -242,7 +242,8 @@ int mi_cls_spec_compile(const void *tbl, size_t bytes, int nw);
  * Returns 1 while the compile thread is active, else 0. */
 int mi_cls_spec_pending(uint32_t *running, uint32_t *queued, uint32_t *cached);
 
-/* The kernel instantiation the context's last mi_cls_classify launched
+/* The kernel instantiation the context's last mi_cls_classify (or
+ * mi_cls_parse: see there) launched
  * (diagnostics: bench lines and fault records name it).  info[0] waves per
  * block, [1] 1 if the hot region was in LDS, [2] 1 if the per-lane CoS-tree
  * rounds were compiled in (DIV), [3] flat engine + 1 (0: not a flat
@@ -392,6 +393,72 @@ int mi_cls_chksum_insert_host_submit(mi_cls_ctx_t *ctx, uint8_t *pkts_host, size
 				     const mi_cls_tx_desc_t *desc_host, uint32_t n, uint64_t pktout_opt,
 				     uint8_t *done_host, uint64_t *ticket);
 int mi_cls_chksum_insert_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
+
+/* ------------------------------------------------------------------------
+ * The parse on its own: odp_packet_parse() / odp_packet_parse_multi() for a
+ * batch (reference odp_packet.c:2140-2229 over odp_parse.c:23-105 _odp_parse_eth
+ * and :362-488 _odp_packet_parse_common_l3_l4, then odp_packet.c:2065-2138
+ * _odp_packet_l4_chksum).  No rule program takes part and the context needs
+ * no rules.  Per call:
+ *   proto       where the parse starts: an Ethernet header, or an IPv4 / IPv6
+ *               header (then no L2 flag is set and l3_offset is 0);
+ *   last_layer  where it stops: L2 (the return at odp_parse.c:372-375: L2
+ *               flags and the snap-length error, l4_offset invalid), L3 (:412:
+ *               also the L3 flags, the IP and IPv4-checksum errors and
+ *               l4_offset as the L3 parsers set it), L4 or ALL (the same);
+ *   chksums     odp_proto_chksums_t.all_chksum: bit 0 ipv4, 1 udp, 2 tcp, 3
+ *               sctp -- the checksums to validate (no drop rules).
+ * The caller folds a packet's parse offset into the batch: off[i] is the
+ * byte where parsing starts and len[i] = frame_len - offset (every length
+ * odp_parse.c tests is relative to that); any alignment.  The batch contract
+ * of mi_cls_classify holds (readable up to each frame's 16-B rounding).
+ * The record: in_flags, err, l3_offset / l4_offset relative to the parse
+ * start (0xFFFF invalid); outcome MI_CLS_OUT_ENQ where odp_packet_parse
+ * returns 0, MI_CLS_OUT_PARSE_DROP where it returns -1 (an error bit left
+ * after the layer cut, or a truncated TCP / UDP / SCTP header at layer >= L4,
+ * which sets none); cos, hops, queue, mark 0.
+ * ---------------------------------------------------------------------- */
+#define MI_CLS_PROTO_ETH  1u   /* odp_proto_t */
+#define MI_CLS_PROTO_IPV4 2u
+#define MI_CLS_PROTO_IPV6 3u
+#define MI_CLS_LAYER_L2   1u   /* odp_proto_layer_t */
+#define MI_CLS_LAYER_L3   2u
+#define MI_CLS_LAYER_L4   3u
+#define MI_CLS_LAYER_ALL  4u
+#define MI_CLS_CHKSUM_IPV4 1u  /* odp_proto_chksums_t.all_chksum */
+#define MI_CLS_CHKSUM_UDP  2u
+#define MI_CLS_CHKSUM_TCP  4u
+#define MI_CLS_CHKSUM_SCTP 8u
+
+typedef struct mi_cls_parse_param {
+	uint32_t proto;         /* MI_CLS_PROTO_*                                   */
+	uint32_t last_layer;    /* MI_CLS_LAYER_*                                   */
+	uint32_t chksums;       /* MI_CLS_CHKSUM_* bits (others ignored)            */
+} mi_cls_parse_param_t;
+
+/* Parse n packets in device memory; out_dev 16-byte aligned.  Stream-ordered
+ * on `stream`; returns after the launch is enqueued.  n == 0: 0.  proto or
+ * last_layer out of range: -EINVAL.  No device: -ENODEV.  mi_cls_last_launch
+ * reports this launch too: info[0] 4, [1]-[4] 0, [5] 1 when checksum code
+ * ran, [6] the grid. */
+int mi_cls_parse(mi_cls_ctx_t *ctx, const uint8_t *pkts_dev, const uint32_t *off_dev,
+		 const uint16_t *len_dev, uint32_t n, const mi_cls_parse_param_t *param,
+		 mi_cls_result_t *out_dev, void *stream);
+
+/* Host-memory batch, with the semantics of mi_cls_chksum_insert_host and its
+ * submit / wait forms: pkts_host, off_host, len_host and out_host page-locked
+ * (mi_cls_host_alloc) and every frame's 16-B rounding inside `bytes`: read
+ * and written in place; otherwise through the context's staging buffers
+ * (nothing is copied back but the records: a parse writes no frame byte).
+ * Tickets come from the context's ring. */
+int mi_cls_parse_host(mi_cls_ctx_t *ctx, const uint8_t *pkts_host, size_t bytes,
+		      const uint32_t *off_host, const uint16_t *len_host, uint32_t n,
+		      const mi_cls_parse_param_t *param, mi_cls_result_t *out_host);
+int mi_cls_parse_host_submit(mi_cls_ctx_t *ctx, const uint8_t *pkts_host, size_t bytes,
+			     const uint32_t *off_host, const uint16_t *len_host, uint32_t n,
+			     const mi_cls_parse_param_t *param, mi_cls_result_t *out_host,
+			     uint64_t *ticket);
+int mi_cls_parse_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
 
 /* ------------------------------------------------------------------------
  * Receive delivery on the GPU: the host steps of loopback_recv /

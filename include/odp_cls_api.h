@@ -328,6 +328,20 @@ int odp_amd_cls_chksum_insert_host(odp_pktio_t pktio, uint8_t *pkts, size_t byte
 				   const struct mi_cls_tx_desc *desc, uint32_t n, uint64_t pktout_opt,
 				   uint8_t *done);
 
+/* The parse on its own for a batch in host memory (mi_cls_parse_host): no
+ * pktio, no rules, no device pointers.  off[i] is the byte where packet i's
+ * parse starts, len[i] its frame length less its parse offset; proto /
+ * last_layer / chksums are odp_proto_t / odp_proto_layer_t /
+ * odp_proto_chksums_t.all_chksum; out: n mi_cls_result_t.  Runs on one
+ * process-wide context, created by the first call on the device ODP_AMD_GPU
+ * names (default 0), one call at a time (a mutex); odp_amd_cls_parse_term
+ * (odp_term_global) destroys it.  Synchronous.  0 or a negative errno
+ * (-ENODEV: no GPU). */
+int odp_amd_cls_parse_host(const uint8_t *pkts, size_t bytes, const uint32_t *off,
+			   const uint16_t *len, uint32_t n, uint32_t proto, uint32_t last_layer,
+			   uint32_t chksums, void *out);
+void odp_amd_cls_parse_term(void);
+
 /* Create the device context, upload the current rule snapshot and run a
  * warm-up launch (odp_pktio_start). */
 int odp_amd_cls_prepare(odp_pktio_t pktio, int parse_only);

@@ -524,6 +524,131 @@ int odp_packet_has_icmp(odp_packet_t pkt);
 int odp_packet_has_flow_hash(odp_packet_t pkt);
 int odp_packet_has_ts(odp_packet_t pkt);
 
+/* Parsing a packet the application holds (include/odp/api/spec/packet.h,
+ * packet_types.h; reference odp_packet.c:2140-2290): one it built, a
+ * decapsulated inner header, a re-parse after an edit.  The parse runs on the
+ * GPU (mi_cls_parse): one kernel launch per call, whatever `num` is, on a
+ * process-wide context on the device ODP_AMD_GPU names.  There is no CPU
+ * parser: without a GPU the calls fail (-1 / 0) and say so once. */
+typedef enum odp_proto_t {
+	ODP_PROTO_NONE = 0,
+	ODP_PROTO_ETH,          /* Ethernet, VLAN tags included */
+	ODP_PROTO_IPV4,
+	ODP_PROTO_IPV6
+} odp_proto_t;
+
+/* the checksums a parse validates */
+typedef union odp_proto_chksums_t {
+	struct {
+		uint32_t ipv4 : 1;
+		uint32_t udp  : 1;
+		uint32_t tcp  : 1;
+		uint32_t sctp : 1;
+	} chksum;
+	uint32_t all_chksum;
+} odp_proto_chksums_t;
+
+typedef struct odp_packet_parse_param_t {
+	odp_proto_t proto;              /* header at the parse start: ETH, IPV4, IPV6 */
+	odp_proto_layer_t last_layer;   /* parse up to and including this layer */
+	odp_proto_chksums_t chksums;    /* status: odp_packet_l3/l4_chksum_status() */
+} odp_packet_parse_param_t;
+
+typedef uint8_t odp_proto_l2_type_t;
+#define ODP_PROTO_L2_TYPE_NONE 0
+#define ODP_PROTO_L2_TYPE_ETH  1
+
+typedef uint16_t odp_proto_l3_type_t;   /* the ethertype */
+#define ODP_PROTO_L3_TYPE_NONE 0xFFFF
+#define ODP_PROTO_L3_TYPE_ARP  0x0806
+#define ODP_PROTO_L3_TYPE_RARP 0x8035
+#define ODP_PROTO_L3_TYPE_MPLS 0x8847
+#define ODP_PROTO_L3_TYPE_IPV4 0x0800
+#define ODP_PROTO_L3_TYPE_IPV6 0x86DD
+
+typedef uint8_t odp_proto_l4_type_t;    /* the IP protocol number */
+#define ODP_PROTO_L4_TYPE_NONE    255
+#define ODP_PROTO_L4_TYPE_ICMPV4  1
+#define ODP_PROTO_L4_TYPE_IGMP    2
+#define ODP_PROTO_L4_TYPE_IPV4    4
+#define ODP_PROTO_L4_TYPE_TCP     6
+#define ODP_PROTO_L4_TYPE_UDP     17
+#define ODP_PROTO_L4_TYPE_IPV6    41
+#define ODP_PROTO_L4_TYPE_GRE     47
+#define ODP_PROTO_L4_TYPE_ESP     50
+#define ODP_PROTO_L4_TYPE_AH      51
+#define ODP_PROTO_L4_TYPE_ICMPV6  58
+#define ODP_PROTO_L4_TYPE_NO_NEXT 59
+#define ODP_PROTO_L4_TYPE_IPCOMP  108
+#define ODP_PROTO_L4_TYPE_SCTP    132
+#define ODP_PROTO_L4_TYPE_ROHC    142
+
+/* each flag is the odp_packet_has_<name>() of the same name */
+typedef struct odp_packet_parse_result_flag_t {
+	union {
+		uint64_t all;
+		struct {
+			uint64_t has_error     : 1;
+			uint64_t has_l2_error  : 1;
+			uint64_t has_l3_error  : 1;
+			uint64_t has_l4_error  : 1;
+			uint64_t has_l2        : 1;
+			uint64_t has_l3        : 1;
+			uint64_t has_l4        : 1;
+			uint64_t has_eth       : 1;
+			uint64_t has_eth_bcast : 1;
+			uint64_t has_eth_mcast : 1;
+			uint64_t has_jumbo     : 1;
+			uint64_t has_vlan      : 1;
+			uint64_t has_vlan_qinq : 1;
+			uint64_t has_arp       : 1;
+			uint64_t has_ipv4      : 1;
+			uint64_t has_ipv6      : 1;
+			uint64_t has_ip_bcast  : 1;
+			uint64_t has_ip_mcast  : 1;
+			uint64_t has_ipfrag    : 1;
+			uint64_t has_ipopt     : 1;
+			uint64_t has_ipsec     : 1;
+			uint64_t has_udp       : 1;
+			uint64_t has_tcp       : 1;
+			uint64_t has_sctp      : 1;
+			uint64_t has_icmp      : 1;
+		};
+	};
+} odp_packet_parse_result_flag_t;
+
+typedef struct odp_packet_parse_result_t {
+	odp_packet_parse_result_flag_t flag;
+	uint32_t packet_len;
+	uint32_t l2_offset;
+	uint32_t l3_offset;
+	uint32_t l4_offset;
+	odp_packet_chksum_status_t l3_chksum_status;
+	odp_packet_chksum_status_t l4_chksum_status;
+	odp_proto_l2_type_t l2_type;
+	odp_proto_l3_type_t l3_type;
+	odp_proto_l4_type_t l4_type;
+} odp_packet_parse_result_t;
+
+/* Parse from byte `offset` of the packet.  The parser's metadata is replaced
+ * (every input flag -- a classifier mark too --, the error bits, the l2 / l3
+ * / l4 offsets); the user pointer and the pktout checksum overrides stay.
+ * 0, or -1: proto / last_layer NONE, offset past the packet (nothing is
+ * touched then), no GPU, or a packet with a parse error (its metadata is
+ * written).  _multi parses pkt[i] from offset[i] and returns the number of
+ * packets parsed without a failure before the first one that failed; that
+ * one carries its metadata, the packets after it are not touched. */
+int odp_packet_parse(odp_packet_t pkt, uint32_t offset, const odp_packet_parse_param_t *param);
+int odp_packet_parse_multi(const odp_packet_t pkt[], const uint32_t offset[], int num,
+			   const odp_packet_parse_param_t *param);
+/* host only, from the packet's metadata */
+void odp_packet_parse_result(odp_packet_t pkt, odp_packet_parse_result_t *result);
+void odp_packet_parse_result_multi(const odp_packet_t pkt[], odp_packet_parse_result_t *result[],
+				   int num);
+odp_proto_l2_type_t odp_packet_l2_type(odp_packet_t pkt);
+odp_proto_l3_type_t odp_packet_l3_type(odp_packet_t pkt);
+odp_proto_l4_type_t odp_packet_l4_type(odp_packet_t pkt);
+
 /* ------------------------------------------------------------ queues */
 typedef enum odp_queue_type_t {
 	ODP_QUEUE_TYPE_PLAIN = 0,
@@ -904,6 +1029,9 @@ int odp_amd_pktio_rx_idle(odp_pktio_t pktio);
  * and how many of them went through the bounce buffer (a packet outside the
  * page-locked pools); 0, or -1 on a bad handle. */
 int odp_amd_pktio_tx_stats(odp_pktio_t pktio, uint64_t *bursts, uint64_t *bounced);
+/* odp_packet_parse / _multi calls of the process that ran the parse kernel,
+ * and how many of them went through the bounce buffer. */
+void odp_amd_packet_parse_stats(uint64_t *calls, uint64_t *bounced);
 
 #ifdef __cplusplus
 }

@@ -97,6 +97,17 @@ class Capability(C.Structure):
                 ("max_mark", C.c_uint64), ("stats_cos", C.c_uint64), ("stats_queue", C.c_uint64)]
 
 
+class ParseParam(C.Structure):
+    """mi_cls_parse_param_t."""
+    _fields_ = [("proto", C.c_uint32), ("last_layer", C.c_uint32), ("chksums", C.c_uint32)]
+
+
+# odp_proto_t, odp_proto_layer_t, odp_proto_chksums_t.all_chksum
+PROTO_ETH, PROTO_IPV4, PROTO_IPV6 = 1, 2, 3
+LAYER_L2, LAYER_L3, LAYER_L4, LAYER_ALL = 1, 2, 3, 4
+CHKSUM_IPV4, CHKSUM_UDP, CHKSUM_TCP, CHKSUM_SCTP = 1, 2, 4, 8
+
+
 def _load():
     for p in (LIB_MI, LIB_ODP):
         if not os.path.exists(p):
@@ -158,6 +169,13 @@ def _load():
         "mi_cls_chksum_insert_host_submit": (i32, [vp, vp, C.c_size_t, vp, vp, vp, u32, C.c_uint64, vp,
                                                    C.POINTER(C.c_uint64)]),
         "mi_cls_chksum_insert_host_wait": (i32, [vp, C.c_uint64]),
+        "mi_cls_parse": (i32, [vp, vp, vp, vp, u32, C.POINTER(ParseParam), vp, vp]),
+        "mi_cls_parse_host": (i32, [vp, vp, C.c_size_t, vp, vp, u32, C.POINTER(ParseParam), vp]),
+        "mi_cls_parse_host_submit": (i32, [vp, vp, C.c_size_t, vp, vp, u32, C.POINTER(ParseParam), vp,
+                                           C.POINTER(C.c_uint64)]),
+        "mi_cls_parse_host_wait": (i32, [vp, C.c_uint64]),
+        "odp_amd_cls_parse_host": (i32, [vp, C.c_size_t, vp, vp, u32, u32, u32, u32, vp]),
+        "odp_amd_cls_parse_term": (None, []),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -295,6 +313,79 @@ def chksum_insert(batch, desc, opt, gpu: int = 0):
         return c.insert(batch, desc, opt, device=f"cuda:{gpu}")
     finally:
         c.close()
+
+
+class ParseContext:
+    """A device context for the parse on its own (mi_cls_parse and its host
+    entries: odp_packet_parse for a batch); needs no rules."""
+
+    def __init__(self, gpu: int = 0):
+        self.L = lib()
+        self.gpu = gpu
+        ctx = C.c_void_p()
+        rc = self.L.mi_cls_ctx_create(gpu, C.byref(ctx))
+        if rc:
+            raise RuntimeError(f"mi_cls_ctx_create: {rc} ({self.L.mi_cls_strerror(rc).decode()})")
+        self.ctx = ctx
+
+    def close(self):
+        if self.ctx:
+            self.L.mi_cls_ctx_destroy(self.ctx)
+            self.ctx = None
+
+    def parse_device(self, d_buf, d_off, d_len, n, proto, last_layer, chksums, d_out, stream=0):
+        """On device pointers (ints), stream-ordered.  Returns the C status."""
+        pp = ParseParam(proto, last_layer, chksums)
+        return self.L.mi_cls_parse(self.ctx, d_buf, d_off, d_len, n, C.byref(pp), d_out, stream or None)
+
+    def parse(self, batch, proto=PROTO_ETH, last_layer=LAYER_ALL, chksums=0):
+        """Upload a pktgen.Batch (off[i]: where packet i's parse starts,
+        len[i]: its frame length less the parse offset), parse it, return the
+        records (rules.RESULT_DTYPE)."""
+        import torch
+        dev = torch.device(f"cuda:{self.gpu}")
+        n = batch.n
+        t_buf = torch.from_numpy(np.ascontiguousarray(batch.buf)).to(dev)
+        t_off = torch.from_numpy(batch.off.astype(np.uint32).view(np.int32)).to(dev)
+        t_len = torch.from_numpy(batch.len.astype(np.uint16).view(np.int16)).to(dev)
+        t_out = torch.zeros((max(1, n), 16), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.parse_device(t_buf.data_ptr(), t_off.data_ptr(), t_len.data_ptr(), n, proto,
+                               last_layer, chksums, t_out.data_ptr(), stream)
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_parse: {rc} ({self.L.mi_cls_strerror(rc).decode()})")
+        torch.cuda.synchronize(dev)
+        return t_out.cpu().numpy().reshape(-1).view(R.RESULT_DTYPE)[:n].copy()
+
+    def parse_host(self, buf, off, ln, out, proto=PROTO_ETH, last_layer=LAYER_ALL, chksums=0):
+        """mi_cls_parse_host on numpy arrays (views of a PinnedArray are read
+        and written in place, other arrays go through the staging buffers)."""
+        pp = ParseParam(proto, last_layer, chksums)
+        rc = self.L.mi_cls_parse_host(self.ctx, buf.ctypes.data, buf.nbytes, off.ctypes.data,
+                                      ln.ctypes.data, int(off.shape[0]), C.byref(pp), out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_parse_host: {rc}")
+
+    def submit_host(self, buf, off, ln, out, proto=PROTO_ETH, last_layer=LAYER_ALL, chksums=0):
+        """mi_cls_parse_host_submit: returns the ticket for wait()."""
+        pp = ParseParam(proto, last_layer, chksums)
+        t = C.c_uint64()
+        rc = self.L.mi_cls_parse_host_submit(self.ctx, buf.ctypes.data, buf.nbytes, off.ctypes.data,
+                                             ln.ctypes.data, int(off.shape[0]), C.byref(pp),
+                                             out.ctypes.data, C.byref(t))
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_parse_host_submit: {rc}")
+        return t.value
+
+    def wait(self, ticket):
+        rc = self.L.mi_cls_parse_host_wait(self.ctx, ticket)
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_parse_host_wait: {rc}")
+
+    def last_launch(self):
+        info = (C.c_uint32 * 7)()
+        self.L.mi_cls_last_launch(self.ctx, info, 7)
+        return list(info)
 
 
 class Classifier:

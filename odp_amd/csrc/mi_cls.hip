@@ -138,6 +138,9 @@ static int preload_kernels(int device)
 	chk(mi_cls_launch_rx_chain(nullptr, ra, mi_cls_rxdev_t{}, true));
 	chk(mi_cls_launch_rx_stage(nullptr, ra, mi_cls_rxdev_t{}, 0, true));
 	chk(mi_cls_launch_tx(0, nullptr, TxArgs{}));
+	for (uint32_t proto : { MI_CLS_PROTO_ETH, MI_CLS_PROTO_IPV4, MI_CLS_PROTO_IPV6 })
+		for (int ck = 0; ck < 2; ++ck)
+			chk(mi_cls_launch_parse(proto, ck != 0, 0, nullptr, ParseArgs{}));
 	if (bad)
 		return bad;
 	done.insert(device);
@@ -1069,6 +1072,154 @@ extern "C" int mi_cls_chksum_insert_host_submit(mi_cls_ctx_t *c, uint8_t *pkts, 
 }
 
 extern "C" int mi_cls_chksum_insert_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
+{
+	if (!c)
+		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
+	return mi_cls_classify_host_wait(c, ticket);
+}
+
+// ------------------------------------------------------ the parse on its own
+static int parse_check(const mi_cls_ctx_t *c, const mi_cls_parse_param_t *pp)
+{
+	// the parameters first: a bad one is -EINVAL with or without a device
+	if (!pp || pp->proto < MI_CLS_PROTO_ETH || pp->proto > MI_CLS_PROTO_IPV6 ||
+	    pp->last_layer < MI_CLS_LAYER_L2 || pp->last_layer > MI_CLS_LAYER_ALL)
+		return -EINVAL;
+	if (!c)
+		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
+	return 0;
+}
+
+extern "C" int mi_cls_parse(mi_cls_ctx_t *c, const uint8_t *pkts, const uint32_t *off,
+			    const uint16_t *len, uint32_t n, const mi_cls_parse_param_t *pp,
+			    mi_cls_result_t *out, void *stream)
+{
+	int rc = parse_check(c, pp);
+	if (rc)
+		return rc;
+	if (n == 0)
+		return 0;
+	if (!pkts || !off || !len || !out || ((uintptr_t)out & 15u) != 0)
+		return -EINVAL;
+	HIP_OK(set_device(c->device));
+	ParseArgs a;
+	a.pkts = pkts;
+	a.off = off;
+	a.len = len;
+	a.out = out;
+	a.n = n;
+	a.layer = pp->last_layer;
+	// odp_proto_chksums_t bits 0-3 are the pktin option bits 2-5; what the
+	// layer leaves of the selection: nothing at L2 (the return precedes
+	// parse_ipv4), the IPv4 header checksum at L3
+	uint32_t ck = (pp->chksums & 0xFu) << 2;
+	if (pp->last_layer == MI_CLS_LAYER_L2)
+		ck = 0;
+	else if (pp->last_layer == MI_CLS_LAYER_L3)
+		ck &= OPT_IPV4_CK;
+	a.opt = ck;
+	// one wave per 64-packet tile, persistent over the tiles: the blocks of
+	// PRS_NW waves a CU holds at once, 4 (3 with the checksum code: its
+	// registers and its 41 KB of LDS admit 3 waves per SIMD)
+	const uint32_t tiles = (n + WAVE - 1) / WAVE;
+	const uint32_t blocks = (tiles + PRS_NW - 1) / PRS_NW;
+	const uint32_t max_grid = (uint32_t)c->num_cu * (ck ? 3u : 4u);
+	const uint32_t grid = blocks < max_grid ? blocks : max_grid;
+	uint32_t *last = c->last;
+	last[0] = PRS_NW;
+	last[1] = last[2] = last[3] = last[4] = 0;
+	last[5] = ck != 0;
+	last[6] = grid;
+	rc = mi_cls_launch_parse(pp->proto, ck != 0, grid, (hipStream_t)stream, a);
+	if (rc)
+		return rc;
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+// A host batch on the context's stream, nothing waited for: in place when
+// everything is page-locked and every frame's 16-B rounding lies inside the
+// buffer, else through the staging buffers (only the records come back).
+static int parse_host_launch(mi_cls_ctx_t *c, const uint8_t *pkts, size_t bytes, const uint32_t *off,
+			     const uint16_t *len, uint32_t n, const mi_cls_parse_param_t *pp,
+			     mi_cls_result_t *out)
+{
+	HIP_OK(set_device(c->device));
+	const void *zp = dev_view(pkts), *zo = zp ? dev_view(off) : nullptr;
+	const void *zl = zo ? dev_view(len) : nullptr, *zr = zl ? dev_view(out) : nullptr;
+	for (uint32_t i = 0; zr && i < n; ++i)
+		if ((size_t)off[i] + (((size_t)len[i] + 15u) & ~(size_t)15u) > bytes)
+			zr = nullptr;
+	if (zr && ((uintptr_t)zr & 15u) == 0)
+		return mi_cls_parse(c, (const uint8_t *)zp, (const uint32_t *)zo, (const uint16_t *)zl, n, pp,
+				    (mi_cls_result_t *)zr, c->stream);
+	int rc = stage_bufs(c, bytes + 64, n);
+	if (rc)
+		return rc;
+	hipStream_t s = c->stream;
+	HIP_OK(hipMemcpyAsync(c->d_pk, pkts, bytes, hipMemcpyHostToDevice, s));
+	HIP_OK(hipMemcpyAsync(c->d_off, off, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+	HIP_OK(hipMemcpyAsync(c->d_len, len, n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+	rc = mi_cls_parse(c, c->d_pk, c->d_off, c->d_len, n, pp, c->d_out, s);
+	if (rc)
+		return rc;
+	HIP_OK(hipMemcpyAsync(out, c->d_out, n * sizeof(mi_cls_result_t), hipMemcpyDeviceToHost, s));
+	return 0;
+}
+
+static int parse_host_check(const mi_cls_ctx_t *c, const uint8_t *pkts, size_t bytes, const uint32_t *off,
+			    const uint16_t *len, uint32_t n, const mi_cls_parse_param_t *pp,
+			    const mi_cls_result_t *out)
+{
+	int rc = parse_check(c, pp);
+	if (rc || n == 0)
+		return rc;
+	if (!pkts || !off || !len || !out)
+		return -EINVAL;
+	for (uint32_t i = 0; i < n; ++i)
+		if ((size_t)off[i] + len[i] > bytes)
+			return -EINVAL;
+	return 0;
+}
+
+extern "C" int mi_cls_parse_host(mi_cls_ctx_t *c, const uint8_t *pkts, size_t bytes, const uint32_t *off,
+				 const uint16_t *len, uint32_t n, const mi_cls_parse_param_t *pp,
+				 mi_cls_result_t *out)
+{
+	int rc = parse_host_check(c, pkts, bytes, off, len, n, pp, out);
+	if (rc || n == 0)
+		return rc;
+	rc = parse_host_launch(c, pkts, bytes, off, len, n, pp, out);
+	if (rc)
+		return rc;
+	HIP_OK(hipStreamSynchronize(c->stream));
+	return 0;
+}
+
+extern "C" int mi_cls_parse_host_submit(mi_cls_ctx_t *c, const uint8_t *pkts, size_t bytes,
+					const uint32_t *off, const uint16_t *len, uint32_t n,
+					const mi_cls_parse_param_t *pp, mi_cls_result_t *out,
+					uint64_t *ticket)
+{
+	if (!ticket)
+		return -EINVAL;
+	*ticket = 0;
+	int rc = parse_host_check(c, pkts, bytes, off, len, n, pp, out);
+	if (rc || n == 0)
+		return rc;
+	const uint64_t t = c->submitted + 1;
+	HIP_OK(set_device(c->device));
+	if (ring_slot(c, t))
+		return -EIO;
+	rc = parse_host_launch(c, pkts, bytes, off, len, n, pp, out);
+	if (rc)
+		return rc;
+	HIP_OK(hipEventRecord(c->ev[t % 8], c->stream));
+	c->submitted = t;
+	*ticket = t;
+	return 0;
+}
+
+extern "C" int mi_cls_parse_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
 {
 	if (!c)
 		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;

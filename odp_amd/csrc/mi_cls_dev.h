@@ -175,48 +175,57 @@ __device__ __forceinline__ uint32_t ck_finalize(uint64_t s)
 // errors; the UDP zero-checksum rule of parse_udp), odp_parse.c:23-105,
 // 112-354, 362-488; contiguous packet so seg_end == frame_len.  The L4
 // checksums themselves are l4_chksum() below.
+// START (odp_packet_parse's start protocol, mi_cls_kp.hip): MI_CLS_PROTO_IPV4 /
+// _IPV6 skip _odp_parse_eth -- the parse is _odp_packet_parse_common_l3_l4
+// with ethertype 0x0800 / 0x86DD and L3 at byte 0, no L2 flag is set
+// (odp_packet.c:2184-2195).
+template <uint32_t START = MI_CLS_PROTO_ETH>
 __device__ __forceinline__ Parsed parse_packet(const Pkt &k, uint32_t opt)
 {
 	Parsed r;
 	const uint32_t len = k.len;
-	uint32_t f = F_L2 | F_ETH, err = 0, off = 14, ethtype, ip_proto = 255;
+	constexpr bool ETH = START == MI_CLS_PROTO_ETH;
+	uint32_t f = ETH ? (F_L2 | F_ETH) : 0u, err = 0, off = ETH ? 14u : 0u, ip_proto = 255;
+	uint32_t ethtype = START == MI_CLS_PROTO_IPV4 ? 0x0800u : 0x86DDu;
 	bool non_first = false;
 	r.udp_zero = 0;
 
 	r.l4 = 0xFFFFu;
-	uint32_t w0 = r32(k, 0), w1 = r32(k, 4);
-	if (len > 1514u)
-		f |= F_JUMBO;
-	if (w0 & 1u)
-		f |= F_ETH_MCAST;
-	if (w0 == 0xffffffffu && (w1 & 0xffffu) == 0xffffu)
-		f |= F_ETH_BCAST;
-	ethtype = be16(k, 12);
-	bool snap_err = false;
-	if (ethtype < 1514u) {
-		if (ethtype > len - 14u) {
-			err |= E_SNAP;
-			ethtype = 0;
-			snap_err = true;
-		} else {
-			ethtype = be16(k, 20);
-			off = 22;
+	if constexpr (ETH) {
+		uint32_t w0 = r32(k, 0), w1 = r32(k, 4);
+		if (len > 1514u)
+			f |= F_JUMBO;
+		if (w0 & 1u)
+			f |= F_ETH_MCAST;
+		if (w0 == 0xffffffffu && (w1 & 0xffffu) == 0xffffu)
+			f |= F_ETH_BCAST;
+		ethtype = be16(k, 12);
+		bool snap_err = false;
+		if (ethtype < 1514u) {
+			if (ethtype > len - 14u) {
+				err |= E_SNAP;
+				ethtype = 0;
+				snap_err = true;
+			} else {
+				ethtype = be16(k, 20);
+				off = 22;
+			}
 		}
-	}
-	if (!snap_err) {
-		if (ethtype == 0x88A8u) {
-			f |= F_QINQ | F_VLAN;
-			ethtype = be16(k, off + 2);
-			off += 4;
-		}
-		if (ethtype == 0x8100u) {
-			f |= F_VLAN;
-			ethtype = be16(k, off + 2);
-			off += 4;
-		}
-		if (off > len) {
-			f = F_L2;
-			ethtype = 0;
+		if (!snap_err) {
+			if (ethtype == 0x88A8u) {
+				f |= F_QINQ | F_VLAN;
+				ethtype = be16(k, off + 2);
+				off += 4;
+			}
+			if (ethtype == 0x8100u) {
+				f |= F_VLAN;
+				ethtype = be16(k, off + 2);
+				off += 4;
+			}
+			if (off > len) {
+				f = F_L2;
+				ethtype = 0;
+			}
 		}
 	}
 
@@ -2771,6 +2780,20 @@ struct TxArgs {
 };
 #define TX_NW 4             // waves per block
 int mi_cls_launch_tx(unsigned grid, hipStream_t st, const TxArgs &a);
+
+// the parse on its own (mi_cls_parse; kernel: mi_cls_parse_dev.h,
+// mi_cls_kp.hip).  grid == 0: preload only.
+struct ParseArgs {
+	const uint8_t *pkts;
+	const uint32_t *off;    // the byte parsing starts at
+	const uint16_t *len;    // frame_len - parse offset
+	mi_cls_result_t *out;
+	uint32_t n;
+	uint32_t layer;         // MI_CLS_LAYER_L2..ALL
+	uint32_t opt;           // the checksum selection as pktin option bits (OPT_*_CK)
+};
+#define PRS_NW 4            // waves per block
+int mi_cls_launch_parse(uint32_t proto, bool ck, unsigned grid, hipStream_t st, const ParseArgs &a);
 
 // Every launcher goes through mi_launch.  grid == 0 launches nothing: it
 // resolves the instantiation on the current device (hipFuncGetAttributes

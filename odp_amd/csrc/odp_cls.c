@@ -1646,6 +1646,43 @@ int odp_amd_cls_chksum_insert_host(odp_pktio_t h, uint8_t *pkts, size_t bytes, c
 	return mi_cls_chksum_insert_host(e->tctx, pkts, bytes, off, len, desc, n, pktout_opt, done);
 }
 
+/* The parse on its own (odp_packet_parse, mi_cls_parse_host) on one
+ * process-wide context: created by the first call on the device ODP_AMD_GPU
+ * names (default 0), used under its mutex (the context's staging buffers and
+ * stream are one batch's at a time), destroyed by odp_amd_cls_parse_term
+ * (odp_term_global).  No pktio and no rules take part.  Synchronous. */
+static struct {
+	pthread_mutex_t lock;
+	mi_cls_ctx_t *ctx;
+} PARSE = { PTHREAD_MUTEX_INITIALIZER, NULL };
+
+int odp_amd_cls_parse_host(const uint8_t *pkts, size_t bytes, const uint32_t *off, const uint16_t *len,
+			   uint32_t n, uint32_t proto, uint32_t last_layer, uint32_t chksums, void *out)
+{
+	const mi_cls_parse_param_t pp = { proto, last_layer, chksums };
+	int rc = 0;
+
+	pthread_mutex_lock(&PARSE.lock);
+	if (!PARSE.ctx) {
+		const char *g = getenv("ODP_AMD_GPU");
+
+		rc = mi_cls_ctx_create(g ? atoi(g) : 0, &PARSE.ctx);
+	}
+	if (!rc)
+		rc = mi_cls_parse_host(PARSE.ctx, pkts, bytes, off, len, n, &pp, (mi_cls_result_t *)out);
+	pthread_mutex_unlock(&PARSE.lock);
+	return rc;
+}
+
+void odp_amd_cls_parse_term(void)
+{
+	pthread_mutex_lock(&PARSE.lock);
+	if (PARSE.ctx)
+		mi_cls_ctx_destroy(PARSE.ctx);
+	PARSE.ctx = NULL;
+	pthread_mutex_unlock(&PARSE.lock);
+}
+
 /* GPU receive delivery of a classified burst (mi_cls_deliver_submit) on the
  * pktio's (first) device; waited for with odp_amd_cls_classify_host_wait. */
 int odp_amd_cls_deliver(odp_pktio_t h, const mi_cls_dlv_args_t *args, uint64_t *ticket)

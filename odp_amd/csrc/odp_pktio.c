@@ -3277,6 +3277,159 @@ out:
 	return rc;
 }
 
+/* ============================================================ odp_packet_parse */
+/* The descriptors, records and bounce buffer of odp_packet_parse_multi:
+ * process-wide, as the parse context (odp_amd_cls_parse_host), one call at a
+ * time; page-locked where there is a GPU; kept for the process's life. */
+static struct {
+	pthread_mutex_t lock;
+	uint8_t *arr;
+	mi_cls_result_t *res;   /* arr: records, offsets, lengths */
+	uint32_t *off;
+	uint16_t *len;
+	uint32_t cap;
+	int pinned;
+	uint8_t *stage;
+	size_t stage_cap;
+	int stage_pinned;
+	int no_gpu_said;
+	uint64_t calls, bounced;   /* kernel launches / of them through the bounce buffer */
+} PRS = { .lock = PTHREAD_MUTEX_INITIALIZER };
+
+/* odp_packet_parse_multi (odp_packet.c:2219-2229 over odp_packet_parse,
+ * :2140-2217) with one kernel launch for the whole call: the packets'
+ * descriptors -- the byte the parse starts at, relative to the page-locked
+ * arena, and frame_len - offset -- are built in page-locked memory and the
+ * kernel reads the frames in place; a call with a packet outside the arena
+ * (pageable pools) goes through a page-locked bounce buffer, as tx_chksum
+ * (nothing is copied back: a parse writes no frame byte).  Then, in order,
+ * each packet is reset as packet_parse_reset(hdr, 0) and takes its record's
+ * metadata, up to and including the first packet whose parse failed; the
+ * packets after that one stay as they were (the reference's loop ends
+ * there). */
+int odp_packet_parse_multi(const odp_packet_t pkts[], const uint32_t offset[], int num,
+			   const odp_packet_parse_param_t *param)
+{
+	if (num <= 0 || !param || param->proto == ODP_PROTO_NONE || param->last_layer == ODP_PROTO_LAYER_NONE)
+		return 0;
+	/* odp_packet_parse stops at a packet whose offset is past its data
+	 * (packet_map returns NULL) before touching it: nothing from there on
+	 * is parsed */
+	uint32_t n = 0;
+
+	while (n < (uint32_t)num && offset[n] < rt_pkt_hdr(pkts[n])->len)
+		n++;
+	if (n == 0)
+		return 0;
+	int done = 0;
+
+	pthread_mutex_lock(&PRS.lock);
+	if (n > PRS.cap) {
+		const size_t cap = n < 1024u ? 1024u : (size_t)n + n / 2;
+
+		hmem_free(PRS.arr, PRS.pinned);
+		PRS.cap = 0;
+		PRS.arr = hmem_alloc(cap * (sizeof(mi_cls_result_t) + sizeof(uint32_t) + sizeof(uint16_t)),
+				     &PRS.pinned);
+		if (!PRS.arr)
+			goto out;
+		PRS.res = (mi_cls_result_t *)(void *)PRS.arr;
+		PRS.off = (uint32_t *)(void *)(PRS.res + cap);
+		PRS.len = (uint16_t *)(void *)(PRS.off + cap);
+		PRS.cap = (uint32_t)cap;
+	}
+	uint8_t *lo = NULL;
+	const uint8_t *base;
+	size_t span = 0, bytes = 0;
+	int in_place = PRS.pinned && rt_pinned_arena(&lo, &span) && span < OOB_SPAN;
+
+	for (uint32_t i = 0; i < n; i++) {
+		const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
+		const uint8_t *d = h->head + h->data_off + offset[i];
+		const uint32_t rest = h->len - offset[i];
+		const uint32_t l = rest > 65535 ? 65535 : rest;
+		const rt_pool_t *rp = rt_pool((odp_pool_t)(uintptr_t)(h->ev.pool + 1u));
+
+		PRS.len[i] = (uint16_t)l;
+		if (in_place && rp && rp->pinned && d >= lo && (size_t)(d - lo) + l + 16u <= span)
+			PRS.off[i] = (uint32_t)(d - lo);
+		else
+			in_place = 0;
+		bytes += (l + 63u) & ~63u;
+	}
+	if (in_place) {
+		base = lo;
+		bytes = span;
+	} else {
+		bytes += 64;
+		if (bytes >= OOB_SPAN)
+			goto out;
+		if (bytes > PRS.stage_cap) {
+			hmem_free(PRS.stage, PRS.stage_pinned);
+			PRS.stage_cap = 0;
+			PRS.stage = hmem_alloc(bytes + bytes / 2, &PRS.stage_pinned);
+			if (!PRS.stage)
+				goto out;
+			PRS.stage_cap = bytes + bytes / 2;
+		}
+		size_t off = 0;
+
+		for (uint32_t i = 0; i < n; i++) {
+			const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
+
+			memcpy(PRS.stage + off, h->head + h->data_off + offset[i], PRS.len[i]);
+			PRS.off[i] = (uint32_t)off;
+			off += (PRS.len[i] + 63u) & ~63u;
+		}
+		base = PRS.stage;
+	}
+	const int rc = odp_amd_cls_parse_host(base, bytes, PRS.off, PRS.len, n, (uint32_t)param->proto,
+					      (uint32_t)param->last_layer, param->chksums.all_chksum & 0xFu,
+					      PRS.res);
+
+	if (rc) {
+		/* no CPU parser stands in (as odp_pktio_start without a GPU) */
+		if (rc != -ENODEV || !PRS.no_gpu_said)
+			RT_ERR("odp_packet_parse: GPU parse unavailable (%s)\n", mi_cls_strerror(rc));
+		PRS.no_gpu_said |= rc == -ENODEV;
+		goto out;
+	}
+	PRS.calls++;
+	PRS.bounced += !in_place;
+	for (uint32_t i = 0; i < n; i++) {
+		pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
+		const mi_cls_result_t *r = &PRS.res[i];
+		const uint32_t o = offset[i];
+
+		/* packet_parse_reset(hdr, 0): the input flags and error bits are
+		 * replaced whole; user_ptr and the pktout overrides (tx_ck) stay */
+		h->in_flags = r->in_flags;
+		h->err = r->err;
+		h->l2 = param->proto == ODP_PROTO_ETH ? (uint16_t)o : ODP_PACKET_OFFSET_INVALID;
+		h->l3 = r->l3_offset == 0xFFFFu ? ODP_PACKET_OFFSET_INVALID : (uint16_t)(r->l3_offset + o);
+		h->l4 = r->l4_offset == 0xFFFFu ? ODP_PACKET_OFFSET_INVALID : (uint16_t)(r->l4_offset + o);
+		if (r->outcome != MI_CLS_OUT_ENQ)
+			break;
+		done++;
+	}
+out:
+	pthread_mutex_unlock(&PRS.lock);
+	return done;
+}
+
+int odp_packet_parse(odp_packet_t pkt, uint32_t offset, const odp_packet_parse_param_t *param)
+{
+	return odp_packet_parse_multi(&pkt, &offset, 1, param) == 1 ? 0 : -1;
+}
+
+void odp_amd_packet_parse_stats(uint64_t *calls, uint64_t *bounced)
+{
+	pthread_mutex_lock(&PRS.lock);
+	*calls = PRS.calls;
+	*bounced = PRS.bounced;
+	pthread_mutex_unlock(&PRS.lock);
+}
+
 int odp_pktout_send(odp_pktout_queue_t q, const odp_packet_t pkts[], int num)
 {
 	rt_pktio_t *e = get_pk(q.pktio);

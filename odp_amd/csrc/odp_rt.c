@@ -124,6 +124,7 @@ int odp_term_local(void)
 int odp_term_global(odp_instance_t instance)
 {
 	(void)instance;
+	odp_amd_cls_parse_term();   /* odp_packet_parse's GPU context */
 	RT.init = 0;
 	return 0;
 }
@@ -1299,6 +1300,93 @@ void odp_packet_l4_chksum_insert(odp_packet_t pkt, int insert)
 
 	h->tx_ck = (uint16_t)((h->tx_ck & ~(MI_CLS_TXF_L4_SET | MI_CLS_TXF_L4)) | MI_CLS_TXF_L4_SET |
 			      (insert ? MI_CLS_TXF_L4 : 0u));
+}
+
+/* packet_inlines.h:338-387: the protocol types from the input flags */
+odp_proto_l2_type_t odp_packet_l2_type(odp_packet_t pkt)
+{
+	return odp_packet_has_eth(pkt) ? ODP_PROTO_L2_TYPE_ETH : ODP_PROTO_L2_TYPE_NONE;
+}
+
+odp_proto_l3_type_t odp_packet_l3_type(odp_packet_t pkt)
+{
+	if (odp_packet_has_ipv4(pkt))
+		return ODP_PROTO_L3_TYPE_IPV4;
+	if (odp_packet_has_ipv6(pkt))
+		return ODP_PROTO_L3_TYPE_IPV6;
+	if (odp_packet_has_arp(pkt))
+		return ODP_PROTO_L3_TYPE_ARP;
+	return ODP_PROTO_L3_TYPE_NONE;
+}
+
+odp_proto_l4_type_t odp_packet_l4_type(odp_packet_t pkt)
+{
+	const uint64_t f = rt_pkt_hdr(pkt)->in_flags;
+	const int icmp = odp_packet_has_icmp(pkt);
+
+	if (odp_packet_has_tcp(pkt))
+		return ODP_PROTO_L4_TYPE_TCP;
+	if (odp_packet_has_udp(pkt))
+		return ODP_PROTO_L4_TYPE_UDP;
+	if (odp_packet_has_sctp(pkt))
+		return ODP_PROTO_L4_TYPE_SCTP;
+	if ((f >> 20) & 1u)     /* ipsec_ah */
+		return ODP_PROTO_L4_TYPE_AH;
+	if ((f >> 21) & 1u)     /* ipsec_esp */
+		return ODP_PROTO_L4_TYPE_ESP;
+	if (icmp && odp_packet_has_ipv4(pkt))
+		return ODP_PROTO_L4_TYPE_ICMPV4;
+	if (icmp && odp_packet_has_ipv6(pkt))
+		return ODP_PROTO_L4_TYPE_ICMPV6;
+	if ((f >> 26) & 1u)     /* no_next_hdr */
+		return ODP_PROTO_L4_TYPE_NO_NEXT;
+	return ODP_PROTO_L4_TYPE_NONE;
+}
+
+/* odp_packet.c:2231-2282: host only, from the metadata */
+void odp_packet_parse_result(odp_packet_t pkt, odp_packet_parse_result_t *r)
+{
+	r->flag.all = 0;
+	r->flag.has_error = odp_packet_has_error(pkt);
+	r->flag.has_l2_error = odp_packet_has_l2_error(pkt);
+	r->flag.has_l3_error = odp_packet_has_l3_error(pkt);
+	r->flag.has_l4_error = odp_packet_has_l4_error(pkt);
+	r->flag.has_l2 = odp_packet_has_l2(pkt);
+	r->flag.has_l3 = odp_packet_has_l3(pkt);
+	r->flag.has_l4 = odp_packet_has_l4(pkt);
+	r->flag.has_eth = odp_packet_has_eth(pkt);
+	r->flag.has_eth_bcast = odp_packet_has_eth_bcast(pkt);
+	r->flag.has_eth_mcast = odp_packet_has_eth_mcast(pkt);
+	r->flag.has_jumbo = odp_packet_has_jumbo(pkt);
+	r->flag.has_vlan = odp_packet_has_vlan(pkt);
+	r->flag.has_vlan_qinq = odp_packet_has_vlan_qinq(pkt);
+	r->flag.has_arp = odp_packet_has_arp(pkt);
+	r->flag.has_ipv4 = odp_packet_has_ipv4(pkt);
+	r->flag.has_ipv6 = odp_packet_has_ipv6(pkt);
+	r->flag.has_ip_bcast = odp_packet_has_ip_bcast(pkt);
+	r->flag.has_ip_mcast = odp_packet_has_ip_mcast(pkt);
+	r->flag.has_ipfrag = odp_packet_has_ipfrag(pkt);
+	r->flag.has_ipopt = odp_packet_has_ipopt(pkt);
+	r->flag.has_ipsec = odp_packet_has_ipsec(pkt);
+	r->flag.has_udp = odp_packet_has_udp(pkt);
+	r->flag.has_tcp = odp_packet_has_tcp(pkt);
+	r->flag.has_sctp = odp_packet_has_sctp(pkt);
+	r->flag.has_icmp = odp_packet_has_icmp(pkt);
+	r->packet_len = odp_packet_len(pkt);
+	r->l2_offset = odp_packet_l2_offset(pkt);
+	r->l3_offset = odp_packet_l3_offset(pkt);
+	r->l4_offset = odp_packet_l4_offset(pkt);
+	r->l3_chksum_status = odp_packet_l3_chksum_status(pkt);
+	r->l4_chksum_status = odp_packet_l4_chksum_status(pkt);
+	r->l2_type = odp_packet_l2_type(pkt);
+	r->l3_type = odp_packet_l3_type(pkt);
+	r->l4_type = odp_packet_l4_type(pkt);
+}
+
+void odp_packet_parse_result_multi(const odp_packet_t pkt[], odp_packet_parse_result_t *result[], int num)
+{
+	for (int i = 0; i < num; i++)
+		odp_packet_parse_result(pkt[i], result[i]);
 }
 
 /* accessor for odp_cls_hash_result (odp_cls.c) */
