@@ -461,6 +461,126 @@ int mi_cls_parse_host_submit(mi_cls_ctx_t *ctx, const uint8_t *pkts_host, size_t
 int mi_cls_parse_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
 
 /* ------------------------------------------------------------------------
+ * LSO: large send offload segmentation of a batch (reference
+ * odp_packet_io.c:3089-3152 _odp_lso_num_packets, :3154-3251
+ * _odp_lso_create_packets, :2985-3018 lso_update_ipv4, :3020-3087
+ * lso_update_custom).  A source packet of `len` bytes with a header of
+ * hdr_len bytes is cut into nseg segments: each is the header followed by
+ * seg_payload bytes of the payload (the last one by what is left), and its
+ * header is then edited by the packet's profile:
+ *   IPv4    tot_len = (uint16_t)(seg_len - l3); fragment word = the stored one
+ *           + (k * seg_payload) / 8 in 16 bits, MF added for k < nseg - 1;
+ *           the header checksum recomputed over 20 bytes at l3 + 10.  A header
+ *           whose IHL is not 5 fails the packet (MI_CLS_LSO_ST_IHL).
+ *   custom  up to 8 fields in order, a later one seeing what an earlier one
+ *           wrote: ADD_SEGMENT_NUM adds k to a big-endian 1/2/4/8-byte field
+ *           (wrapping), WRITE_BITS sets (b & ~mask) | (value & mask) in one
+ *           byte with the first (k == 0) / last (k == nseg - 1) / middle pair.
+ *           A field that reaches past the packet's shortest (last) segment
+ *           fails the packet (MI_CLS_LSO_ST_FIELD).
+ * A failed packet's segments are not written; st[i] tells.
+ * ---------------------------------------------------------------------- */
+#define MI_CLS_LSO_MAX_SEGMENTS 64u        /* PKTIO_LSO_MAX_SEGMENTS            */
+#define MI_CLS_LSO_MAX_PAYLOAD_OFFSET 128u /* PKTIO_LSO_MAX_PAYLOAD_OFFSET      */
+#define MI_CLS_LSO_PROFILES 16u            /* PKTIO_LSO_PROFILES                */
+#define MI_CLS_LSO_MAX_CUSTOM 8u           /* ODP_LSO_MAX_CUSTOM                */
+#define MI_CLS_LSO_PROTO_CUSTOM 1u         /* odp_lso_protocol_t                */
+#define MI_CLS_LSO_PROTO_IPV4 2u
+#define MI_CLS_LSO_ADD_SEGMENT_NUM 1u      /* odp_lso_modify_t                  */
+#define MI_CLS_LSO_WRITE_BITS 5u
+#define MI_CLS_LSO_L3_INVALID 0xFFFFu
+
+/* st[i] */
+#define MI_CLS_LSO_ST_OK 0u
+#define MI_CLS_LSO_ST_IHL 1u    /* IPv4 profile: IHL != 5                          */
+#define MI_CLS_LSO_ST_FIELD 2u  /* custom field past a segment's end               */
+#define MI_CLS_LSO_ST_DESC 3u   /* descriptor the kernel refuses (device form only:
+				 * the host forms reject it before the launch)   */
+
+typedef struct mi_cls_lso_field {
+	uint8_t mod_op;         /* MI_CLS_LSO_ADD_SEGMENT_NUM / _WRITE_BITS          */
+	uint8_t offset;         /* from the frame start, <= 128                      */
+	uint8_t size;           /* 1, 2, 4, 8 (WRITE_BITS: 1)                        */
+	uint8_t rsv;
+	uint8_t mask[3];        /* WRITE_BITS: first, middle, last segment           */
+	uint8_t value[3];
+	uint8_t rsv2[2];
+} mi_cls_lso_field_t;   /* 12 B */
+
+typedef struct mi_cls_lso_profile {
+	uint8_t proto;          /* MI_CLS_LSO_PROTO_*                                */
+	uint8_t num_custom;     /* <= 8                                              */
+	uint8_t rsv[2];
+	mi_cls_lso_field_t field[8];
+} mi_cls_lso_profile_t; /* 100 B */
+
+/* One source packet (16 B, 16-byte aligned). */
+typedef struct mi_cls_lso_desc {
+	uint16_t hdr_len;       /* payload offset, <= 128                            */
+	uint16_t seg_payload;   /* payload bytes per full segment (mi_cls_lso_plan)  */
+	uint16_t l3;            /* IPv4 profile: the IP header's offset              */
+	uint8_t  profile;       /* index into the profile table                      */
+	uint8_t  nseg;          /* 2..64                                             */
+	uint32_t first_seg;     /* its first entry of the segment table              */
+	uint32_t rsv;
+} mi_cls_lso_desc_t;
+
+/* One segment: where it goes and whose it is (segment k of source `src` is
+ * entry desc[src].first_seg + k). */
+typedef struct mi_cls_lso_seg {
+	uint32_t off;           /* byte offset in the destination buffer             */
+	uint32_t src;           /* index of its source packet                        */
+} mi_cls_lso_seg_t;     /* 8 B */
+
+/* Host-only (no device needed): the segmentation plan of one packet,
+ * _odp_lso_num_packets (odp_packet_io.c:3089-3152).  proto MI_CLS_LSO_PROTO_*,
+ * l3 the packet's L3 offset (MI_CLS_LSO_L3_INVALID: none; read for IPv4 only).
+ * Returns the number of segments (1: the packet goes out as it is;
+ * *seg_payload = max_payload, *left_over = 0) or -EINVAL.  Deviation: a
+ * payload length of 0 (max_payload 0, or IPv4 with max_payload < 8), on which
+ * the reference divides by zero, is -EINVAL. */
+int mi_cls_lso_plan(uint32_t len, uint32_t hdr_len, uint32_t max_payload, uint32_t proto, uint32_t l3,
+		    uint32_t *seg_payload, uint32_t *left_over);
+
+/* Segment n source packets in device memory into nsegs segments.  src_dev /
+ * off_dev / len_dev under the batch contract of mi_cls_classify (the kernel
+ * reads no byte outside [off, off + len)); desc_dev 16-byte and seg_dev
+ * 8-byte aligned; dst_dev may be src_dev, no segment overlapping a source
+ * frame or another segment; st_dev n bytes.  Exactly the bytes
+ * [seg.off, seg.off + seg_len) of every segment are written.  The profile
+ * table (nprof <= 16, host memory) travels by value with the launch.
+ * Stream-ordered on `stream`.  n == 0 or nsegs == 0: 0.  No device: -ENODEV.
+ * nprof > 16, a profile's protocol, num_custom, a field's mod_op, offset or
+ * size out of range: -EINVAL before any launch (the host forms check the
+ * descriptors the same way: profile index, nseg 2..64, hdr_len, the segment
+ * table and every source and segment inside its buffer).
+ * mi_cls_last_launch: info[0] 64 + the waves per block (68), [1]-[5] 0, [6]
+ * the grid. */
+int mi_cls_lso_segment(mi_cls_ctx_t *ctx, const uint8_t *src_dev, const uint32_t *off_dev,
+		       const uint16_t *len_dev, const mi_cls_lso_desc_t *desc_dev, uint32_t n,
+		       uint8_t *dst_dev, const mi_cls_lso_seg_t *seg_dev, uint32_t nsegs,
+		       const mi_cls_lso_profile_t *prof, uint32_t nprof, uint8_t *st_dev, void *stream);
+
+/* Host-memory batch, with the semantics of mi_cls_chksum_insert_host and its
+ * submit / wait forms.  src_host (src_bytes) and dst_host (dst_bytes) are
+ * either one buffer (equal pointers and sizes) or two that do not overlap.
+ * All of src, dst, off, len, desc, seg and st page-locked (mi_cls_host_alloc):
+ * worked on in place; otherwise through the context's staging buffers, and
+ * only the destination segments (and st) are copied back. */
+int mi_cls_lso_segment_host(mi_cls_ctx_t *ctx, const uint8_t *src_host, size_t src_bytes,
+			    const uint32_t *off_host, const uint16_t *len_host,
+			    const mi_cls_lso_desc_t *desc_host, uint32_t n, uint8_t *dst_host,
+			    size_t dst_bytes, const mi_cls_lso_seg_t *seg_host, uint32_t nsegs,
+			    const mi_cls_lso_profile_t *prof, uint32_t nprof, uint8_t *st_host);
+int mi_cls_lso_segment_host_submit(mi_cls_ctx_t *ctx, const uint8_t *src_host, size_t src_bytes,
+				   const uint32_t *off_host, const uint16_t *len_host,
+				   const mi_cls_lso_desc_t *desc_host, uint32_t n, uint8_t *dst_host,
+				   size_t dst_bytes, const mi_cls_lso_seg_t *seg_host, uint32_t nsegs,
+				   const mi_cls_lso_profile_t *prof, uint32_t nprof, uint8_t *st_host,
+				   uint64_t *ticket);
+int mi_cls_lso_segment_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
+
+/* ------------------------------------------------------------------------
  * Receive delivery on the GPU: the host steps of loopback_recv /
  * pcapif_recv_pkt after classification (pktio/loop.c:308-373, pcap.c:
  * 330-352) for packets whose headers and buffers are in page-locked host

@@ -328,6 +328,18 @@ int odp_amd_cls_chksum_insert_host(odp_pktio_t pktio, uint8_t *pkts, size_t byte
 				   const struct mi_cls_tx_desc *desc, uint32_t n, uint64_t pktout_opt,
 				   uint8_t *done);
 
+/* LSO segmentation of a send call on the pktio's transmit context, the one
+ * odp_amd_cls_chksum_insert_host uses (mi_cls_lso_segment_host: sources and
+ * segments in one buffer; a sender never shares a stream with a receive
+ * burst); the context is created by the first call.  Synchronous. */
+struct mi_cls_lso_desc;
+struct mi_cls_lso_seg;
+struct mi_cls_lso_profile;
+int odp_amd_cls_lso_segment_host(odp_pktio_t pktio, uint8_t *buf, size_t bytes, const uint32_t *off,
+				 const uint16_t *len, const struct mi_cls_lso_desc *desc, uint32_t n,
+				 const struct mi_cls_lso_seg *seg, uint32_t nsegs,
+				 const struct mi_cls_lso_profile *prof, uint32_t nprof, uint8_t *st);
+
 /* The parse on its own for a batch in host memory (mi_cls_parse_host): no
  * pktio, no rules, no device pointers.  off[i] is the byte where packet i's
  * parse starts, len[i] its frame length less its parse offset; proto /

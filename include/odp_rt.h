@@ -913,6 +913,86 @@ typedef struct odp_reass_config_t {
 	uint8_t max_num_frags;
 } odp_reass_config_t;
 
+/* LSO (include/odp/api/spec/packet_io_types.h:778-987, 1181-1256;
+ * packet_types.h:465-497) */
+#define ODP_LSO_MAX_CUSTOM 8
+
+typedef enum odp_lso_modify_t {
+	ODP_LSO_ADD_SEGMENT_NUM = 0x1,
+	ODP_LSO_ADD_PAYLOAD_LEN = 0x2,
+	ODP_LSO_ADD_PAYLOAD_OFFSET = 0x4,
+	ODP_LSO_WRITE_BITS
+} odp_lso_modify_t;
+
+typedef enum odp_lso_protocol_t {
+	ODP_LSO_PROTO_NONE = 0,
+	ODP_LSO_PROTO_CUSTOM,
+	ODP_LSO_PROTO_IPV4,
+	ODP_LSO_PROTO_IPV6,
+	ODP_LSO_PROTO_TCP_IPV4,
+	ODP_LSO_PROTO_TCP_IPV6,
+	ODP_LSO_PROTO_SCTP_IPV4,
+	ODP_LSO_PROTO_SCTP_IPV6
+} odp_lso_protocol_t;
+
+typedef struct odp_lso_capability_t {
+	uint32_t max_profiles;
+	uint32_t max_profiles_per_pktio;
+	uint32_t max_packet_segments;
+	uint32_t max_segments;
+	uint32_t max_payload_len;
+	uint32_t max_payload_offset;
+	struct {
+		uint16_t add_segment_num : 1;
+		uint16_t add_payload_len : 1;
+		uint16_t add_payload_offset : 1;
+		uint16_t write_bits : 1;
+	} mod_op;
+	uint8_t max_num_custom;
+	struct {
+		uint32_t custom : 1;
+		uint32_t ipv4 : 1;
+		uint32_t ipv6 : 1;
+		uint32_t tcp_ipv4 : 1;
+		uint32_t tcp_ipv6 : 1;
+		uint32_t sctp_ipv4 : 1;
+		uint32_t sctp_ipv6 : 1;
+	} proto;
+} odp_lso_capability_t;
+
+typedef struct odp_lso_write_bits_t {
+	uint8_t mask[1];
+	uint8_t value[1];   /* new = (old & ~mask) | (value & mask) */
+} odp_lso_write_bits_t;
+
+typedef struct odp_lso_profile_param_t {
+	odp_lso_protocol_t lso_proto;
+	struct {
+		struct {
+			odp_lso_modify_t mod_op;
+			uint32_t offset;
+			uint8_t size;
+			union {
+				struct {
+					odp_lso_write_bits_t first_seg;
+					odp_lso_write_bits_t middle_seg;
+					odp_lso_write_bits_t last_seg;
+				} write_bits;
+			};
+		} field[ODP_LSO_MAX_CUSTOM];
+		uint8_t num_custom;
+	} custom;
+} odp_lso_profile_param_t;
+
+typedef struct odp_lso_profile_s *odp_lso_profile_t;
+#define ODP_LSO_PROFILE_INVALID ((odp_lso_profile_t)0)
+
+typedef struct odp_packet_lso_opt_t {
+	odp_lso_profile_t lso_profile;
+	uint32_t payload_offset;
+	uint32_t max_payload_len;
+} odp_packet_lso_opt_t;
+
 typedef struct odp_pktio_config_t {
 	odp_pktin_config_opt_t pktin;
 	odp_pktout_config_opt_t pktout;
@@ -961,6 +1041,7 @@ typedef struct odp_pktio_capability_t {
 	} maxlen;
 	odp_support_t loop_supported;
 	odp_bool_t vector_supported;
+	odp_lso_capability_t lso;
 } odp_pktio_capability_t;
 
 typedef struct odp_pktio_stats_t {
@@ -1010,6 +1091,21 @@ int odp_pktin_recv(odp_pktin_queue_t queue, odp_packet_t packets[], int num);
 int odp_pktin_recv_tmo(odp_pktin_queue_t queue, odp_packet_t packets[], int num, uint64_t wait);
 uint64_t odp_pktin_wait_time(uint64_t nsec);
 int odp_pktout_send(odp_pktout_queue_t queue, const odp_packet_t packets[], int num);
+/* LSO (odp_packet_io.c:2837-3348): the segments of a call are cut, and their
+ * headers edited, by one GPU launch (mi_cls_lso_segment_host); there is no
+ * CPU segmentation: on a pktio that is not started (any pktio where there is
+ * no GPU) odp_pktout_send_lso says so once and returns -1.  Profiles and
+ * per-packet requests need no GPU. */
+void odp_lso_profile_param_init(odp_lso_profile_param_t *param);
+odp_lso_profile_t odp_lso_profile_create(odp_pktio_t pktio, const odp_lso_profile_param_t *param);
+int odp_lso_profile_destroy(odp_lso_profile_t lso_profile);
+int odp_packet_lso_request(odp_packet_t pkt, const odp_packet_lso_opt_t *lso_opt);
+void odp_packet_lso_request_clr(odp_packet_t pkt);
+int odp_packet_has_lso_request(odp_packet_t pkt);
+uint32_t odp_packet_payload_offset(odp_packet_t pkt);
+int odp_packet_payload_offset_set(odp_packet_t pkt, uint32_t offset);
+int odp_pktout_send_lso(odp_pktout_queue_t queue, const odp_packet_t packet[], int num,
+			const odp_packet_lso_opt_t *lso_opt);
 int odp_pktio_promisc_mode(odp_pktio_t pktio);
 int odp_pktio_promisc_mode_set(odp_pktio_t pktio, odp_bool_t enable);
 int odp_pktio_mac_addr(odp_pktio_t pktio, void *mac_addr, int size);
@@ -1029,6 +1125,9 @@ int odp_amd_pktio_rx_idle(odp_pktio_t pktio);
  * and how many of them went through the bounce buffer (a packet outside the
  * page-locked pools); 0, or -1 on a bad handle. */
 int odp_amd_pktio_tx_stats(odp_pktio_t pktio, uint64_t *bursts, uint64_t *bounced);
+/* odp_pktout_send_lso calls of the pktio that ran the LSO kernel, and how many
+ * of them went through the bounce buffer; 0, or -1 on a bad handle. */
+int odp_amd_pktio_lso_stats(odp_pktio_t pktio, uint64_t *bursts, uint64_t *bounced);
 /* odp_packet_parse / _multi calls of the process that ran the parse kernel,
  * and how many of them went through the bounce buffer. */
 void odp_amd_packet_parse_stats(uint64_t *calls, uint64_t *bounced);

@@ -72,11 +72,12 @@ def build(force: bool = False, out_dir: str = PKG, defines=(), src_dir: str = SR
     host_deps = [asm_src, spec_src, prog_hdr, os.path.join(SRC, "mi_cls_asm.h"),
                  os.path.join(SRC, "mi_cls_spec.h")]
     k_srcs = [os.path.join(SRC, f"mi_cls_k{w}.hip") for w in (4, 8, 12, 16, "f", "f12", "f16", "c4",
-                                                              "c16", "d", "t", "p")]
+                                                              "c16", "d", "t", "p", "l")]
     tx_hdr = os.path.join(SRC, "mi_cls_tx_dev.h")
     parse_hdr = os.path.join(SRC, "mi_cls_parse_dev.h")
+    lso_hdr = os.path.join(SRC, "mi_cls_lso_dev.h")
     variant = bool(defines) or src_dir != globals()["SRC"]
-    if force or variant or _stale(mi_so, [mi_src, mi_hdr, tx_hdr, parse_hdr] + host_deps + k_srcs + hdrs + [__file__]):
+    if force or variant or _stale(mi_so, [mi_src, mi_hdr, tx_hdr, parse_hdr, lso_hdr] + host_deps + k_srcs + hdrs + [__file__]):
         # one translation unit per block shape + the host code, compiled in
         # parallel (the kernel instantiations dominate the build time)
         import concurrent.futures as cf
@@ -160,7 +161,7 @@ def build_test_drivers(force: bool = False):
     built = None
     deps = [os.path.join(PKG, "libodp_cls.so"), os.path.join(PKG, "libodph.so"),
             os.path.join(INC, "odp_rt.h"), os.path.join(INC, "odp", "helper", "odph_api.h")]
-    for name in ("rx_driver", "rt_unit", "tx_driver", "parse_driver"):
+    for name in ("rx_driver", "rt_unit", "tx_driver", "parse_driver", "lso_driver"):
         src = os.path.join(ROOT, "tests", "rt", name + ".c")
         if not os.path.exists(src):
             continue

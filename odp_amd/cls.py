@@ -174,6 +174,13 @@ def _load():
         "mi_cls_parse_host_submit": (i32, [vp, vp, C.c_size_t, vp, vp, u32, C.POINTER(ParseParam), vp,
                                            C.POINTER(C.c_uint64)]),
         "mi_cls_parse_host_wait": (i32, [vp, C.c_uint64]),
+        "mi_cls_lso_plan": (i32, [u32, u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]),
+        "mi_cls_lso_segment": (i32, [vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, vp]),
+        "mi_cls_lso_segment_host": (i32, [vp, vp, C.c_size_t, vp, vp, vp, u32, vp, C.c_size_t, vp, u32, vp,
+                                          u32, vp]),
+        "mi_cls_lso_segment_host_submit": (i32, [vp, vp, C.c_size_t, vp, vp, vp, u32, vp, C.c_size_t, vp,
+                                                 u32, vp, u32, vp, C.POINTER(C.c_uint64)]),
+        "mi_cls_lso_segment_host_wait": (i32, [vp, C.c_uint64]),
         "odp_amd_cls_parse_host": (i32, [vp, C.c_size_t, vp, vp, u32, u32, u32, u32, vp]),
         "odp_amd_cls_parse_term": (None, []),
     }
@@ -381,6 +388,124 @@ class ParseContext:
         rc = self.L.mi_cls_parse_host_wait(self.ctx, ticket)
         if rc != 0:
             raise RuntimeError(f"mi_cls_parse_host_wait: {rc}")
+
+    def last_launch(self):
+        info = (C.c_uint32 * 7)()
+        self.L.mi_cls_last_launch(self.ctx, info, 7)
+        return list(info)
+
+
+# LSO (include/mi_cls.h): odp_lso_protocol_t / odp_lso_modify_t values, the
+# per-source descriptor, the segment table entry, st[] values
+LSO_PROTO_CUSTOM, LSO_PROTO_IPV4 = 1, 2
+LSO_ADD_SEGMENT_NUM, LSO_WRITE_BITS = 1, 5
+LSO_L3_INVALID = 0xFFFF
+LSO_ST_OK, LSO_ST_IHL, LSO_ST_FIELD, LSO_ST_DESC = 0, 1, 2, 3
+LSO_DESC_DTYPE = np.dtype([("hdr_len", "<u2"), ("seg_payload", "<u2"), ("l3", "<u2"), ("profile", "u1"),
+                           ("nseg", "u1"), ("first_seg", "<u4"), ("rsv", "<u4")])
+LSO_SEG_DTYPE = np.dtype([("off", "<u4"), ("src", "<u4")])
+
+
+class LsoField(C.Structure):
+    """mi_cls_lso_field_t."""
+    _fields_ = [("mod_op", C.c_uint8), ("offset", C.c_uint8), ("size", C.c_uint8), ("rsv", C.c_uint8),
+                ("mask", C.c_uint8 * 3), ("value", C.c_uint8 * 3), ("rsv2", C.c_uint8 * 2)]
+
+
+class LsoProfile(C.Structure):
+    """mi_cls_lso_profile_t."""
+    _fields_ = [("proto", C.c_uint8), ("num_custom", C.c_uint8), ("rsv", C.c_uint8 * 2),
+                ("field", LsoField * 8)]
+
+
+def lso_profiles(profiles):
+    """A profile table for LsoContext from [(proto, [field, ...])]; a field is
+    (LSO_ADD_SEGMENT_NUM, offset, size) or (LSO_WRITE_BITS, offset, 1,
+    (first, middle, last) masks, (first, middle, last) values)."""
+    arr = (LsoProfile * max(1, len(profiles)))()
+    for p, (proto, fields) in zip(arr, profiles):
+        p.proto = proto
+        p.num_custom = len(fields)
+        for f, spec in zip(p.field, fields):   # more than 8: num_custom tells, the C side rejects
+            f.mod_op, f.offset, f.size = spec[0], spec[1], spec[2]
+            if len(spec) > 3:
+                f.mask[:] = spec[3]
+                f.value[:] = spec[4]
+    return arr
+
+
+def lso_plan(length, hdr_len, max_payload, proto, l3=LSO_L3_INVALID):
+    """mi_cls_lso_plan (host only): (segments, payload per segment, left-over)
+    or (negative errno, 0, 0)."""
+    pay, left = C.c_uint32(), C.c_uint32()
+    rc = lib().mi_cls_lso_plan(length, hdr_len, max_payload, proto, l3, C.byref(pay), C.byref(left))
+    return (rc, pay.value, left.value) if rc > 0 else (rc, 0, 0)
+
+
+class LsoContext:
+    """A device context for the LSO segmentation (mi_cls_lso_segment and its
+    host entries); needs no rules."""
+
+    def __init__(self, gpu: int = 0):
+        self.L = lib()
+        self.gpu = gpu
+        ctx = C.c_void_p()
+        rc = self.L.mi_cls_ctx_create(gpu, C.byref(ctx))
+        if rc:
+            raise RuntimeError(f"mi_cls_ctx_create: {rc} ({self.L.mi_cls_strerror(rc).decode()})")
+        self.ctx = ctx
+
+    def close(self):
+        if self.ctx:
+            self.L.mi_cls_ctx_destroy(self.ctx)
+            self.ctx = None
+
+    plan = staticmethod(lso_plan)
+
+    def segment_device(self, d_src, d_off, d_len, d_desc, n, d_dst, d_seg, nsegs, prof, d_st, stream=0):
+        """On device pointers (ints), stream-ordered; prof: lso_profiles().
+        Returns the C status."""
+        return self.L.mi_cls_lso_segment(self.ctx, d_src, d_off, d_len, d_desc, n, d_dst, d_seg, nsegs,
+                                         C.cast(prof, C.c_void_p), len(prof), d_st, stream or None)
+
+    def segment(self, buf, off, ln, desc, seg, prof):
+        """Upload one buffer holding the sources and room for the segments,
+        its descriptors (LSO_DESC_DTYPE) and segment table (LSO_SEG_DTYPE),
+        segment in place, return (buffer bytes, st bytes) as numpy arrays."""
+        import torch
+        dev = torch.device(f"cuda:{self.gpu}")
+        n, nsegs = int(len(desc)), int(len(seg))
+        desc = np.ascontiguousarray(desc, dtype=LSO_DESC_DTYPE)
+        seg = np.ascontiguousarray(seg, dtype=LSO_SEG_DTYPE)
+        t_buf = torch.from_numpy(np.ascontiguousarray(buf)).to(dev)
+        t_off = torch.from_numpy(np.asarray(off, np.uint32).view(np.int32)).to(dev)
+        t_len = torch.from_numpy(np.asarray(ln, np.uint16).view(np.int16)).to(dev)
+        t_desc = torch.from_numpy(desc.view(np.uint8).reshape(-1, 16).copy() if n
+                                  else np.zeros((1, 16), np.uint8)).to(dev)
+        t_seg = torch.from_numpy(seg.view(np.int64).copy() if nsegs else np.zeros(1, np.int64)).to(dev)
+        t_st = torch.full((max(1, n),), 0xEE, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.segment_device(t_buf.data_ptr(), t_off.data_ptr(), t_len.data_ptr(), t_desc.data_ptr(), n,
+                                 t_buf.data_ptr(), t_seg.data_ptr(), nsegs, prof, t_st.data_ptr(), stream)
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_lso_segment: {rc} ({self.L.mi_cls_strerror(rc).decode()})")
+        torch.cuda.synchronize(dev)
+        return t_buf.cpu().numpy(), t_st.cpu().numpy()[:n]
+
+    def segment_host(self, src, off, ln, desc, dst, seg, prof, st, submit=False):
+        """mi_cls_lso_segment_host on numpy arrays (views of PinnedArrays are
+        worked on in place, other arrays go through the staging buffers); dst
+        (which may be src) and st are written.  Returns the C status."""
+        args = (self.ctx, src.ctypes.data, src.nbytes, off.ctypes.data, ln.ctypes.data, desc.ctypes.data,
+                int(len(desc)), dst.ctypes.data, dst.nbytes, seg.ctypes.data, int(len(seg)),
+                C.cast(prof, C.c_void_p), len(prof), st.ctypes.data)
+        if submit:
+            t = C.c_uint64()
+            rc = self.L.mi_cls_lso_segment_host_submit(*args, C.byref(t))
+            if rc == 0:
+                rc = self.L.mi_cls_lso_segment_host_wait(self.ctx, t.value)
+            return rc
+        return self.L.mi_cls_lso_segment_host(*args)
 
     def last_launch(self):
         info = (C.c_uint32 * 7)()

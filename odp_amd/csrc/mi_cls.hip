@@ -141,6 +141,7 @@ static int preload_kernels(int device)
 	for (uint32_t proto : { MI_CLS_PROTO_ETH, MI_CLS_PROTO_IPV4, MI_CLS_PROTO_IPV6 })
 		for (int ck = 0; ck < 2; ++ck)
 			chk(mi_cls_launch_parse(proto, ck != 0, 0, nullptr, ParseArgs{}));
+	chk(mi_cls_launch_lso(0, nullptr, LsoArgs{}));
 	if (bad)
 		return bad;
 	done.insert(device);
@@ -1220,6 +1221,284 @@ extern "C" int mi_cls_parse_host_submit(mi_cls_ctx_t *c, const uint8_t *pkts, si
 }
 
 extern "C" int mi_cls_parse_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
+{
+	if (!c)
+		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
+	return mi_cls_classify_host_wait(c, ticket);
+}
+
+// ------------------------------------------------------------------------ LSO
+// _odp_lso_num_packets (odp_packet_io.c:3089-3152), its tests in its order.
+extern "C" int mi_cls_lso_plan(uint32_t len, uint32_t hdr_len, uint32_t max_payload, uint32_t proto,
+			       uint32_t l3, uint32_t *seg_payload, uint32_t *left_over)
+{
+	if (!seg_payload || !left_over)
+		return -EINVAL;
+	if (hdr_len > MI_CLS_LSO_MAX_PAYLOAD_OFFSET || hdr_len > len)
+		return -EINVAL;
+	if ((uint64_t)hdr_len + max_payload > len) {   // no segmentation needed (:3110-3116)
+		*seg_payload = max_payload;
+		*left_over = 0;
+		return 1;
+	}
+	uint32_t pay = max_payload;
+	if (proto == MI_CLS_LSO_PROTO_IPV4) {
+		if (l3 == MI_CLS_LSO_L3_INVALID || hdr_len < l3 || hdr_len - l3 < 20u)
+			return -EINVAL;
+		pay &= ~7u;   // a multiple of 8 on every fragment but the last (:3133)
+	}
+	if (pay == 0)   // the reference divides by it (deviations)
+		return -EINVAL;
+	const uint32_t total = len - hdr_len;
+	uint32_t num = total / pay;
+	const uint32_t left = total - num * pay;
+	if (left)
+		++num;
+	if (num > MI_CLS_LSO_MAX_SEGMENTS)
+		return -EINVAL;
+	*seg_payload = pay;
+	*left_over = left;
+	return (int)num;
+}
+
+// What odp_lso_profile_create admits (:2844-2893), of the launch's own table
+static int lso_prof_check(const mi_cls_lso_profile_t *prof, uint32_t nprof)
+{
+	if (!prof || nprof == 0 || nprof > MI_CLS_LSO_PROFILES)
+		return -EINVAL;
+	for (uint32_t p = 0; p < nprof; ++p) {
+		const mi_cls_lso_profile_t &q = prof[p];
+		if (q.proto == 0 && q.num_custom == 0)
+			continue;   // an unused slot: a descriptor naming it is refused
+		if (q.proto != MI_CLS_LSO_PROTO_CUSTOM && q.proto != MI_CLS_LSO_PROTO_IPV4)
+			return -EINVAL;
+		if (q.num_custom > MI_CLS_LSO_MAX_CUSTOM)
+			return -EINVAL;
+		for (uint32_t f = 0; q.proto == MI_CLS_LSO_PROTO_CUSTOM && f < q.num_custom; ++f) {
+			const mi_cls_lso_field_t &d = q.field[f];
+			if (d.offset > MI_CLS_LSO_MAX_PAYLOAD_OFFSET)
+				return -EINVAL;
+			if (d.mod_op != MI_CLS_LSO_ADD_SEGMENT_NUM && d.mod_op != MI_CLS_LSO_WRITE_BITS)
+				return -EINVAL;
+			if (d.mod_op == MI_CLS_LSO_WRITE_BITS ? d.size != 1
+							      : (d.size != 1 && d.size != 2 && d.size != 4 && d.size != 8))
+				return -EINVAL;
+		}
+	}
+	return 0;
+}
+
+extern "C" int mi_cls_lso_segment(mi_cls_ctx_t *c, const uint8_t *src, const uint32_t *off,
+				  const uint16_t *len, const mi_cls_lso_desc_t *desc, uint32_t n,
+				  uint8_t *dst, const mi_cls_lso_seg_t *seg, uint32_t nsegs,
+				  const mi_cls_lso_profile_t *prof, uint32_t nprof, uint8_t *st, void *stream)
+{
+	// the parameters first: a bad table is -EINVAL with or without a device
+	if ((n != 0 && nsegs != 0) || prof) {
+		const int rc = lso_prof_check(prof, nprof);
+		if (rc)
+			return rc;
+	}
+	if (!c)
+		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
+	if (n == 0 || nsegs == 0)
+		return 0;
+	if (!src || !off || !len || !desc || !dst || !seg || !st || ((uintptr_t)desc & 15u) != 0 ||
+	    ((uintptr_t)seg & 7u) != 0)
+		return -EINVAL;
+	HIP_OK(set_device(c->device));
+	LsoArgs a;
+	memset(&a, 0, sizeof(a));
+	a.src = src;
+	a.off = off;
+	a.len = len;
+	a.desc = desc;
+	a.dst = dst;
+	a.seg = seg;
+	a.st = st;
+	a.n = n;
+	a.nsegs = nsegs;
+	a.nprof = nprof;
+	memcpy(a.prof, prof, nprof * sizeof(mi_cls_lso_profile_t));
+	// one wave per segment, persistent over the table: at most 8 blocks of
+	// LSO_NW waves per CU (32 VGPRs: the wave slots bound it)
+	const uint32_t blocks = (nsegs + LSO_NW - 1) / LSO_NW;
+	const uint32_t max_grid = (uint32_t)c->num_cu * 8u;
+	const uint32_t grid = blocks < max_grid ? blocks : max_grid;
+	uint32_t *last = c->last;
+	last[0] = 64u + LSO_NW;
+	last[1] = last[2] = last[3] = last[4] = last[5] = 0;
+	last[6] = grid;
+	const int rc = mi_cls_launch_lso(grid, (hipStream_t)stream, a);
+	if (rc)
+		return rc;
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+// Segment j's length by its descriptor (valid descriptors: lso_host_check)
+static uint32_t lso_seg_len(const mi_cls_lso_desc_t &d, uint32_t len, uint32_t k)
+{
+	return k + 1u < d.nseg ? (uint32_t)d.hdr_len + d.seg_payload
+			       : len - (uint32_t)(d.nseg - 1u) * d.seg_payload;
+}
+
+// The host forms' check: the table, then every descriptor as the kernel
+// expects it (mi_cls_lso_plan's result), every source inside src and every
+// segment inside dst.
+static int lso_host_check(const mi_cls_ctx_t *c, const uint8_t *src, size_t src_bytes, const uint32_t *off,
+			  const uint16_t *len, const mi_cls_lso_desc_t *desc, uint32_t n, const uint8_t *dst,
+			  size_t dst_bytes, const mi_cls_lso_seg_t *seg, uint32_t nsegs,
+			  const mi_cls_lso_profile_t *prof, uint32_t nprof, const uint8_t *st)
+{
+	if ((n != 0 && nsegs != 0) || prof) {
+		const int rc = lso_prof_check(prof, nprof);
+		if (rc)
+			return rc;
+	}
+	if (n == 0 || nsegs == 0)
+		return c ? 0 : (mi_cls_device_count() > 0 ? -EINVAL : -ENODEV);
+	if (!src || !off || !len || !desc || !dst || !seg || !st || ((uintptr_t)desc & 15u) != 0 ||
+	    ((uintptr_t)seg & 7u) != 0)
+		return -EINVAL;
+	if (src == dst ? src_bytes != dst_bytes
+		       : (src < dst ? src + src_bytes > dst : dst + dst_bytes > src))
+		return -EINVAL;
+	uint64_t owned = 0;
+	for (uint32_t i = 0; i < n; ++i) {
+		const mi_cls_lso_desc_t &d = desc[i];
+		if ((size_t)off[i] + len[i] > src_bytes || d.profile >= nprof || d.nseg < 2 ||
+		    d.nseg > MI_CLS_LSO_MAX_SEGMENTS || d.hdr_len > MI_CLS_LSO_MAX_PAYLOAD_OFFSET ||
+		    d.hdr_len > len[i] || d.seg_payload == 0 || (uint64_t)d.first_seg + d.nseg > nsegs)
+			return -EINVAL;
+		const uint32_t total = (uint32_t)len[i] - d.hdr_len, pay = d.seg_payload;
+		if ((uint32_t)(d.nseg - 1u) * pay >= total || total > (uint32_t)d.nseg * pay)
+			return -EINVAL;
+		const uint8_t proto = prof[d.profile].proto;
+		if (proto != MI_CLS_LSO_PROTO_CUSTOM &&
+		    !(proto == MI_CLS_LSO_PROTO_IPV4 && (uint32_t)d.l3 + 20u <= d.hdr_len))
+			return -EINVAL;
+		for (uint32_t k = 0; k < d.nseg; ++k) {
+			const mi_cls_lso_seg_t &s = seg[d.first_seg + k];
+			if (s.src != i || (size_t)s.off + lso_seg_len(d, len[i], k) > dst_bytes)
+				return -EINVAL;
+		}
+		owned += d.nseg;
+	}
+	if (owned != nsegs)
+		return -EINVAL;
+	if (!c)
+		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
+	return 0;
+}
+
+// A host batch on the context's stream: in place when everything is
+// page-locked (*staged = false: nothing waited for); else through the
+// staging buffers -- sources, descriptors and the table up, the kernel, st
+// back, and of the destination only the segments of the packets that did not
+// fail (runs of adjoining segments in one copy).  The staged form has
+// completed when it returns.
+static int lso_host_launch(mi_cls_ctx_t *c, const uint8_t *src, size_t src_bytes, const uint32_t *off,
+			   const uint16_t *len, const mi_cls_lso_desc_t *desc, uint32_t n, uint8_t *dst,
+			   size_t dst_bytes, const mi_cls_lso_seg_t *seg, uint32_t nsegs,
+			   const mi_cls_lso_profile_t *prof, uint32_t nprof, uint8_t *st)
+{
+	HIP_OK(set_device(c->device));
+	const void *zs = dev_view(src), *zd = zs ? dev_view(dst) : nullptr;
+	const void *zo = zd ? dev_view(off) : nullptr, *zl = zo ? dev_view(len) : nullptr;
+	const void *zc = zl ? dev_view(desc) : nullptr, *zg = zc ? dev_view(seg) : nullptr;
+	const void *zt = zg ? dev_view(st) : nullptr;
+	if (zt)
+		return mi_cls_lso_segment(c, (const uint8_t *)zs, (const uint32_t *)zo, (const uint16_t *)zl,
+					  (const mi_cls_lso_desc_t *)zc, n, (uint8_t *)zd,
+					  (const mi_cls_lso_seg_t *)zg, nsegs, prof, nprof, (uint8_t *)zt, c->stream);
+	// d_pk: the sources, then (another buffer) room for the destination, on
+	// a 256-byte boundary; d_out (16 B per entry): the descriptors, then the
+	// segment table; d_len: the lengths, then st
+	const bool same = src == dst;
+	const size_t dbase = same ? 0 : (src_bytes + 255u) & ~(size_t)255u;
+	const uint32_t cnt = 2u * n + nsegs;
+	int rc = stage_bufs(c, dbase + dst_bytes + 64, cnt);
+	if (rc)
+		return rc;
+	hipStream_t s = c->stream;
+	mi_cls_lso_desc_t *d_desc = (mi_cls_lso_desc_t *)c->d_out;
+	mi_cls_lso_seg_t *d_seg = (mi_cls_lso_seg_t *)(c->d_out + n);
+	uint8_t *d_st = (uint8_t *)(c->d_len + n);
+	uint8_t *d_dst = c->d_pk + dbase;
+	HIP_OK(hipMemcpyAsync(c->d_pk, src, src_bytes, hipMemcpyHostToDevice, s));
+	HIP_OK(hipMemcpyAsync(c->d_off, off, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+	HIP_OK(hipMemcpyAsync(c->d_len, len, n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+	HIP_OK(hipMemcpyAsync(d_desc, desc, n * sizeof(mi_cls_lso_desc_t), hipMemcpyHostToDevice, s));
+	HIP_OK(hipMemcpyAsync(d_seg, seg, nsegs * sizeof(mi_cls_lso_seg_t), hipMemcpyHostToDevice, s));
+	rc = mi_cls_lso_segment(c, c->d_pk, c->d_off, c->d_len, d_desc, n, d_dst, d_seg, nsegs, prof, nprof,
+				d_st, s);
+	if (rc)
+		return rc;
+	HIP_OK(hipMemcpyAsync(st, d_st, n, hipMemcpyDeviceToHost, s));
+	HIP_OK(hipStreamSynchronize(s));
+	size_t run_off = 0, run_len = 0;
+	for (uint32_t i = 0; i <= n; ++i) {
+		for (uint32_t k = 0; i < n && st[i] == MI_CLS_LSO_ST_OK && k < desc[i].nseg; ++k) {
+			const size_t o = seg[desc[i].first_seg + k].off, l = lso_seg_len(desc[i], len[i], k);
+			if (run_len && o == run_off + run_len) {
+				run_len += l;
+				continue;
+			}
+			if (run_len)
+				HIP_OK(hipMemcpyAsync(dst + run_off, d_dst + run_off, run_len, hipMemcpyDeviceToHost, s));
+			run_off = o;
+			run_len = l;
+		}
+		if (i == n && run_len)
+			HIP_OK(hipMemcpyAsync(dst + run_off, d_dst + run_off, run_len, hipMemcpyDeviceToHost, s));
+	}
+	HIP_OK(hipStreamSynchronize(s));
+	return 0;
+}
+
+extern "C" int mi_cls_lso_segment_host(mi_cls_ctx_t *c, const uint8_t *src, size_t src_bytes,
+				       const uint32_t *off, const uint16_t *len,
+				       const mi_cls_lso_desc_t *desc, uint32_t n, uint8_t *dst, size_t dst_bytes,
+				       const mi_cls_lso_seg_t *seg, uint32_t nsegs,
+				       const mi_cls_lso_profile_t *prof, uint32_t nprof, uint8_t *st)
+{
+	int rc = lso_host_check(c, src, src_bytes, off, len, desc, n, dst, dst_bytes, seg, nsegs, prof, nprof, st);
+	if (rc || n == 0 || nsegs == 0)
+		return rc;
+	rc = lso_host_launch(c, src, src_bytes, off, len, desc, n, dst, dst_bytes, seg, nsegs, prof, nprof, st);
+	if (rc)
+		return rc;
+	HIP_OK(hipStreamSynchronize(c->stream));
+	return 0;
+}
+
+extern "C" int mi_cls_lso_segment_host_submit(mi_cls_ctx_t *c, const uint8_t *src, size_t src_bytes,
+					      const uint32_t *off, const uint16_t *len,
+					      const mi_cls_lso_desc_t *desc, uint32_t n, uint8_t *dst,
+					      size_t dst_bytes, const mi_cls_lso_seg_t *seg, uint32_t nsegs,
+					      const mi_cls_lso_profile_t *prof, uint32_t nprof, uint8_t *st,
+					      uint64_t *ticket)
+{
+	if (!ticket)
+		return -EINVAL;
+	*ticket = 0;
+	int rc = lso_host_check(c, src, src_bytes, off, len, desc, n, dst, dst_bytes, seg, nsegs, prof, nprof, st);
+	if (rc || n == 0 || nsegs == 0)
+		return rc;
+	const uint64_t t = c->submitted + 1;
+	HIP_OK(set_device(c->device));
+	if (ring_slot(c, t))
+		return -EIO;
+	rc = lso_host_launch(c, src, src_bytes, off, len, desc, n, dst, dst_bytes, seg, nsegs, prof, nprof, st);
+	if (rc)
+		return rc;
+	HIP_OK(hipEventRecord(c->ev[t % 8], c->stream));
+	c->submitted = t;
+	*ticket = t;
+	return 0;
+}
+
+extern "C" int mi_cls_lso_segment_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
 {
 	if (!c)
 		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;

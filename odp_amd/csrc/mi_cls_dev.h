@@ -2795,6 +2795,26 @@ struct ParseArgs {
 #define PRS_NW 4            // waves per block
 int mi_cls_launch_parse(uint32_t proto, bool ck, unsigned grid, hipStream_t st, const ParseArgs &a);
 
+// LSO segmentation (mi_cls_lso_segment; kernel: mi_cls_lso_dev.h,
+// mi_cls_kl.hip).  grid == 0: preload only.  The profile table travels by
+// value in the kernel arguments.
+struct LsoArgs {
+	const uint8_t *src;
+	const uint32_t *off;
+	const uint16_t *len;
+	const mi_cls_lso_desc_t *desc;
+	uint8_t *dst;
+	const mi_cls_lso_seg_t *seg;
+	uint8_t *st;
+	uint32_t n;
+	uint32_t nsegs;
+	uint32_t nprof;
+	uint32_t rsv;
+	mi_cls_lso_profile_t prof[MI_CLS_LSO_PROFILES];
+};
+#define LSO_NW 4            // waves per block
+int mi_cls_launch_lso(unsigned grid, hipStream_t st, const LsoArgs &a);
+
 // Every launcher goes through mi_launch.  grid == 0 launches nothing: it
 // resolves the instantiation on the current device (hipFuncGetAttributes
 // loads the code object that holds it), so mi_cls_ctx_create can load every

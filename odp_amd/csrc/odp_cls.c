@@ -1646,6 +1646,27 @@ int odp_amd_cls_chksum_insert_host(odp_pktio_t h, uint8_t *pkts, size_t bytes, c
 	return mi_cls_chksum_insert_host(e->tctx, pkts, bytes, off, len, desc, n, pktout_opt, done);
 }
 
+/* LSO segmentation of a send call (mi_cls_lso_segment_host) on the pktio's
+ * transmit context, as odp_amd_cls_chksum_insert_host. */
+int odp_amd_cls_lso_segment_host(odp_pktio_t h, uint8_t *buf, size_t bytes, const uint32_t *off,
+				 const uint16_t *len, const mi_cls_lso_desc_t *desc, uint32_t n,
+				 const mi_cls_lso_seg_t *seg, uint32_t nsegs, const mi_cls_lso_profile_t *prof,
+				 uint32_t nprof, uint8_t *st)
+{
+	pktio_t *e = get_pktio(h);
+
+	if (!e)
+		return -EINVAL;
+	if (!e->tctx) {
+		int rc = mi_cls_ctx_create(e->ngpu > 1 ? e->gpus[0] : e->gpu, &e->tctx);
+
+		if (rc)
+			return rc;
+	}
+	return mi_cls_lso_segment_host(e->tctx, buf, bytes, off, len, desc, n, buf, bytes, seg, nsegs, prof,
+				       nprof, st);
+}
+
 /* The parse on its own (odp_packet_parse, mi_cls_parse_host) on one
  * process-wide context: created by the first call on the device ODP_AMD_GPU
  * names (default 0), used under its mutex (the context's staging buffers and

@@ -192,6 +192,20 @@ typedef struct {
 	uint8_t *tx_stage;
 	size_t tx_stage_cap;
 	int tx_stage_pinned;
+	/* LSO (odp_pktout_send_lso): a call's descriptors, segment table and
+	 * status bytes in page-locked memory, and its bounce buffer; under txl */
+	uint8_t *lso_arr;       /* one allocation: lso_desc, lso_seg, lso_off, lso_len, lso_st */
+	mi_cls_lso_desc_t *lso_desc;
+	mi_cls_lso_seg_t *lso_seg;
+	uint32_t *lso_off;
+	uint16_t *lso_len;
+	uint8_t *lso_st;
+	uint32_t lso_cap;       /* sources; 64 segments each */
+	int lso_pinned;
+	uint8_t *lso_stage;
+	size_t lso_stage_cap;
+	int lso_stage_pinned;
+	uint64_t lso_bursts, lso_bounced;   /* as tx_bursts / tx_bounced */
 	uint64_t prof[16];      /* ODP_AMD_RX_PROF: ns staging / classifying / delivering, bursts,
 				 * then of delivering: ns preparing / enqueueing, TSC ticks in
 				 * packet allocation / frame copies; GPU delivery: ns deciding +
@@ -661,6 +675,19 @@ int odp_pktio_capability(odp_pktio_t h, odp_pktio_capability_t *c)
 	c->maxlen.min_input = c->maxlen.min_output = 68 + 14;
 	c->maxlen.max_input = c->maxlen.max_output = 65535;
 	c->loop_supported = ODP_SUPPORT_NO;
+	/* odp_packet_io.c:1566-1577: the same for every driver; packets of this
+	 * runtime have one segment */
+	c->lso.max_profiles = MI_CLS_LSO_PROFILES;
+	c->lso.max_profiles_per_pktio = MI_CLS_LSO_PROFILES;
+	c->lso.max_packet_segments = 1;
+	c->lso.max_segments = MI_CLS_LSO_MAX_SEGMENTS;
+	c->lso.max_payload_len = odp_pktio_mtu(h) - 14;
+	c->lso.max_payload_offset = MI_CLS_LSO_MAX_PAYLOAD_OFFSET;
+	c->lso.mod_op.add_segment_num = 1;
+	c->lso.mod_op.write_bits = 1;
+	c->lso.max_num_custom = ODP_LSO_MAX_CUSTOM;
+	c->lso.proto.ipv4 = 1;
+	c->lso.proto.custom = 1;
 	return 0;
 }
 
@@ -677,11 +704,11 @@ int odp_pktio_config(odp_pktio_t h, const odp_pktio_config_t *config)
 	}
 	/* parser options, pktin checksum validation and drop-on-error options
 	 * (bits 2-10), pktout checksum insertion on a loop pktio (bits 0-7); no
-	 * timestamps, other pktout offloads, IPsec or LSO */
+	 * timestamps, other pktout offloads or IPsec; enable_lso is accepted
+	 * (LSO is common code over every driver, odp_packet_io.c:3305) */
 	if ((config->pktin.all_bits & ~RT_PKTIN_OPT_MASK) ||
 	    (config->pktout.all_bits & ~(e->drv == DRV_LOOP ? RT_PKTOUT_OPT_MASK : 0ull)) ||
-	    config->enable_loop || config->inbound_ipsec || config->outbound_ipsec ||
-	    config->enable_lso) {
+	    config->enable_loop || config->inbound_ipsec || config->outbound_ipsec) {
 		RT_ERR("pktio %s: unsupported configuration option\n", e->name);
 		return -1;
 	}
@@ -1603,6 +1630,10 @@ static void rx_prepare_each(rt_pktio_t *e, rx_set_t *s, int lo, int hi, rx_cnt_t
 		 * no pktout checksum overrides (the GPU deliveries write the whole
 		 * metadata block, this field as 0) */
 		h->tx_ck = 0;
+		h->payload_off = 0;
+		h->lso_flags = 0;
+		h->lso_prof = 0;
+		h->lso_max_payload = 0;
 		h->input = e->hdl;
 		if (!h->err) {
 			c->octets += len;
@@ -3161,6 +3192,12 @@ static void tx_free(rt_pktio_t *e)
 {
 	hmem_free(e->tx_arr, e->tx_pinned);
 	hmem_free(e->tx_stage, e->tx_stage_pinned);
+	hmem_free(e->lso_arr, e->lso_pinned);
+	hmem_free(e->lso_stage, e->lso_stage_pinned);
+	e->lso_arr = NULL;
+	e->lso_stage = NULL;
+	e->lso_cap = 0;
+	e->lso_stage_cap = 0;
 	pthread_mutex_destroy(&e->txl);
 	e->tx_arr = NULL;
 	e->tx_off = NULL;
@@ -3461,6 +3498,484 @@ int odp_pktout_send(odp_pktout_queue_t q, const odp_packet_t pkts[], int num)
 	odp_atomic_add_u64(&e->out_packets, (uint64_t)num);
 	odp_atomic_add_u64(&e->out_octets, octets);
 	return num;
+}
+
+/* ============================================================ LSO */
+/* The LSO profiles (odp_packet_io.c:2837-2950: process-wide, PKTIO_LSO_PROFILES
+ * slots, the handle a slot's address) and their form for the kernel. */
+struct odp_lso_profile_s {
+	int used;
+	odp_lso_profile_param_t param;
+};
+
+static struct {
+	pthread_mutex_t lock;
+	struct odp_lso_profile_s prof[MI_CLS_LSO_PROFILES];
+	uint32_t num;
+	int not_started_said;
+} LSO = { .lock = PTHREAD_MUTEX_INITIALIZER };
+
+void odp_lso_profile_param_init(odp_lso_profile_param_t *param)
+{
+	memset(param, 0, sizeof(*param));
+	param->lso_proto = ODP_LSO_PROTO_NONE;
+}
+
+/* a valid handle's slot index, or -1 */
+static int lso_slot(odp_lso_profile_t h)
+{
+	if (h < &LSO.prof[0] || h >= &LSO.prof[MI_CLS_LSO_PROFILES] ||
+	    ((uintptr_t)h - (uintptr_t)&LSO.prof[0]) % sizeof(LSO.prof[0]))
+		return -1;
+	return (int)(h - &LSO.prof[0]);
+}
+
+odp_lso_profile_t odp_lso_profile_create(odp_pktio_t pktio, const odp_lso_profile_param_t *param)
+{
+	(void)pktio;
+	if (!param)
+		return ODP_LSO_PROFILE_INVALID;
+	/* :2850-2893 */
+	if (param->lso_proto != ODP_LSO_PROTO_IPV4 && param->lso_proto != ODP_LSO_PROTO_CUSTOM) {
+		RT_ERR("LSO protocol %d not supported\n", (int)param->lso_proto);
+		return ODP_LSO_PROFILE_INVALID;
+	}
+	if (param->lso_proto == ODP_LSO_PROTO_CUSTOM) {
+		if (param->custom.num_custom > ODP_LSO_MAX_CUSTOM)
+			return ODP_LSO_PROFILE_INVALID;
+		for (uint32_t i = 0; i < param->custom.num_custom; i++) {
+			const uint32_t op = param->custom.field[i].mod_op, size = param->custom.field[i].size;
+
+			if (param->custom.field[i].offset > MI_CLS_LSO_MAX_PAYLOAD_OFFSET)
+				return ODP_LSO_PROFILE_INVALID;
+			if (op == ODP_LSO_WRITE_BITS ? size != 1 : op != ODP_LSO_ADD_SEGMENT_NUM)
+				return ODP_LSO_PROFILE_INVALID;
+			if (size != 1 && size != 2 && size != 4 && size != 8)
+				return ODP_LSO_PROFILE_INVALID;
+		}
+	}
+	odp_lso_profile_t h = ODP_LSO_PROFILE_INVALID;
+
+	pthread_mutex_lock(&LSO.lock);
+	for (uint32_t i = 0; LSO.num < MI_CLS_LSO_PROFILES && i < MI_CLS_LSO_PROFILES; i++) {
+		if (!LSO.prof[i].used) {
+			LSO.prof[i].used = 1;
+			LSO.prof[i].param = *param;
+			LSO.num++;
+			h = &LSO.prof[i];
+			break;
+		}
+	}
+	pthread_mutex_unlock(&LSO.lock);
+	if (h == ODP_LSO_PROFILE_INVALID)
+		RT_ERR("all %u LSO profiles are in use\n", MI_CLS_LSO_PROFILES);
+	return h;
+}
+
+int odp_lso_profile_destroy(odp_lso_profile_t h)
+{
+	const int i = lso_slot(h);
+	int rc = -1;
+
+	if (i < 0)
+		return -1;
+	pthread_mutex_lock(&LSO.lock);
+	if (LSO.prof[i].used) {
+		LSO.prof[i].used = 0;
+		LSO.num--;
+		rc = 0;
+	}
+	pthread_mutex_unlock(&LSO.lock);
+	return rc;
+}
+
+/* :2952-2983 */
+int odp_packet_lso_request(odp_packet_t pkt, const odp_packet_lso_opt_t *o)
+{
+	pkt_hdr_t *h = rt_pkt_hdr(pkt);
+	const int i = o ? lso_slot(o->lso_profile) : -1;
+
+	if (i < 0 || !LSO.prof[i].used) {
+		RT_ERR("bad LSO profile handle\n");
+		return -1;
+	}
+	if (o->payload_offset > MI_CLS_LSO_MAX_PAYLOAD_OFFSET || o->payload_offset > h->len)
+		return -1;
+	if (odp_packet_payload_offset_set(pkt, o->payload_offset))
+		return -1;
+	h->lso_flags |= RT_LSO_REQ;
+	h->lso_max_payload = o->max_payload_len;
+	h->lso_prof = (uint8_t)i;
+	return 0;
+}
+
+void odp_packet_lso_request_clr(odp_packet_t pkt)
+{
+	rt_pkt_hdr(pkt)->lso_flags &= (uint8_t)~RT_LSO_REQ;
+}
+
+int odp_packet_has_lso_request(odp_packet_t pkt)
+{
+	return (rt_pkt_hdr(pkt)->lso_flags & RT_LSO_REQ) != 0;
+}
+
+/* odp_packet.c:2452-2470 */
+uint32_t odp_packet_payload_offset(odp_packet_t pkt)
+{
+	const pkt_hdr_t *h = rt_pkt_hdr(pkt);
+
+	return (h->lso_flags & RT_LSO_PAYLOAD_OFF) ? h->payload_off : ODP_PACKET_OFFSET_INVALID;
+}
+
+int odp_packet_payload_offset_set(odp_packet_t pkt, uint32_t offset)
+{
+	pkt_hdr_t *h = rt_pkt_hdr(pkt);
+
+	/* the offset is kept in 16 bits, as the reference's (odp_packet_internal.h:142),
+	 * which truncates; here a value that does not fit, or that would read
+	 * back as ODP_PACKET_OFFSET_INVALID, is refused and nothing changes */
+	if (offset >= ODP_PACKET_OFFSET_INVALID)
+		return -1;
+	h->lso_flags |= RT_LSO_PAYLOAD_OFF;
+	h->payload_off = (uint16_t)offset;
+	return 0;
+}
+
+/* The live profiles as the kernel's table (slot i: profile i; an unused
+ * slot stays zero, which no descriptor may name). */
+static void lso_table(mi_cls_lso_profile_t tab[MI_CLS_LSO_PROFILES])
+{
+	memset(tab, 0, MI_CLS_LSO_PROFILES * sizeof(tab[0]));
+	pthread_mutex_lock(&LSO.lock);
+	for (uint32_t i = 0; i < MI_CLS_LSO_PROFILES; i++) {
+		const odp_lso_profile_param_t *p = &LSO.prof[i].param;
+
+		if (!LSO.prof[i].used)
+			continue;
+		tab[i].proto = (uint8_t)p->lso_proto;
+		tab[i].num_custom = p->lso_proto == ODP_LSO_PROTO_CUSTOM ? p->custom.num_custom : 0;
+		for (uint32_t f = 0; f < tab[i].num_custom; f++) {
+			mi_cls_lso_field_t *d = &tab[i].field[f];
+
+			d->mod_op = (uint8_t)p->custom.field[f].mod_op;
+			d->offset = (uint8_t)p->custom.field[f].offset;
+			d->size = p->custom.field[f].size;
+			d->mask[0] = p->custom.field[f].write_bits.first_seg.mask[0];
+			d->mask[1] = p->custom.field[f].write_bits.middle_seg.mask[0];
+			d->mask[2] = p->custom.field[f].write_bits.last_seg.mask[0];
+			d->value[0] = p->custom.field[f].write_bits.first_seg.value[0];
+			d->value[1] = p->custom.field[f].write_bits.middle_seg.value[0];
+			d->value[2] = p->custom.field[f].write_bits.last_seg.value[0];
+		}
+	}
+	pthread_mutex_unlock(&LSO.lock);
+}
+
+/* One source packet of an odp_pktout_send_lso call. */
+typedef struct lso_plan {
+	uint32_t hdr, pay, left, l3;
+	int nseg;               /* 1: goes out whole */
+	uint8_t prof;
+	uint8_t st;             /* the kernel's verdict (MI_CLS_LSO_ST_*), set by lso_launch */
+	uint32_t first;         /* its first segment in the call's segment list */
+} lso_plan_t;
+
+/* Run the LSO kernel for the segmented packets of a call (one launch):
+ * descriptors, segment table and status bytes in page-locked memory; the
+ * frames in place when every source and segment lies in the page-locked
+ * arena, else through a bounce buffer (sources copied in, segments copied
+ * out), with tx_chksum's conditions.  The pktio's arrays are shared by its
+ * senders, so everything that reads them happens under txl: each segmented
+ * packet's verdict is copied into its plan entry (pl[i].st) before the lock
+ * is released.  0, or a negative errno. */
+static int lso_launch(rt_pktio_t *e, const odp_packet_t pkts[], lso_plan_t *pl, int end, uint32_t nsrc,
+		      const odp_packet_t segs[], uint32_t nsegs)
+{
+	mi_cls_lso_profile_t tab[MI_CLS_LSO_PROFILES];
+	int rc = -ENOMEM;
+
+	lso_table(tab);
+	pthread_mutex_lock(&e->txl);
+	if (nsrc > e->lso_cap) {
+		const size_t cap = nsrc < 64u ? 64u : (size_t)nsrc + nsrc / 2;
+
+		hmem_free(e->lso_arr, e->lso_pinned);
+		e->lso_cap = 0;
+		e->lso_arr = hmem_alloc(cap * (sizeof(mi_cls_lso_desc_t) + MI_CLS_LSO_MAX_SEGMENTS * sizeof(mi_cls_lso_seg_t) +
+					       sizeof(uint32_t) + sizeof(uint16_t) + 1u), &e->lso_pinned);
+		if (!e->lso_arr)
+			goto out;
+		e->lso_desc = (mi_cls_lso_desc_t *)(void *)e->lso_arr;
+		e->lso_seg = (mi_cls_lso_seg_t *)(void *)(e->lso_desc + cap);
+		e->lso_off = (uint32_t *)(void *)(e->lso_seg + cap * MI_CLS_LSO_MAX_SEGMENTS);
+		e->lso_len = (uint16_t *)(void *)(e->lso_off + cap);
+		e->lso_st = (uint8_t *)(void *)(e->lso_len + cap);
+		e->lso_cap = (uint32_t)cap;
+	}
+	uint8_t *lo = NULL, *base;
+	size_t span = 0, bytes = 0;
+	int in_place = e->lso_pinned && rt_pinned_arena(&lo, &span) && span < OOB_SPAN;
+	uint32_t k = 0;
+
+	for (int i = 0; i < end; i++) {
+		if (pl[i].nseg < 2)
+			continue;
+		const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
+		const uint8_t *d = h->head + h->data_off;
+		const rt_pool_t *rp = rt_pool((odp_pool_t)(uintptr_t)(h->ev.pool + 1u));
+
+		e->lso_len[k] = (uint16_t)h->len;
+		e->lso_desc[k] = (mi_cls_lso_desc_t){ .hdr_len = (uint16_t)pl[i].hdr, .seg_payload = (uint16_t)pl[i].pay,
+						      .l3 = (uint16_t)pl[i].l3, .profile = pl[i].prof,
+						      .nseg = (uint8_t)pl[i].nseg, .first_seg = pl[i].first };
+		e->lso_st[k] = 0;
+		/* the segments come from the source's pool: one test serves both */
+		if (in_place && rp && rp->pinned && d >= lo && (size_t)(d - lo) + h->len <= span)
+			e->lso_off[k] = (uint32_t)(d - lo);
+		else
+			in_place = 0;
+		bytes += (h->len + 63u) & ~63u;
+		for (int s = 0; s < pl[i].nseg; s++) {
+			const pkt_hdr_t *sh = rt_pkt_hdr(segs[pl[i].first + (uint32_t)s]);
+			const uint8_t *sd = sh->head + sh->data_off;
+
+			e->lso_seg[pl[i].first + (uint32_t)s].src = k;
+			if (in_place && sd >= lo && (size_t)(sd - lo) + sh->len <= span)
+				e->lso_seg[pl[i].first + (uint32_t)s].off = (uint32_t)(sd - lo);
+			else
+				in_place = 0;
+			bytes += (sh->len + 63u) & ~63u;
+		}
+		k++;
+	}
+	if (in_place) {
+		base = lo;
+		bytes = span;
+	} else {
+		bytes += 64;
+		rc = -E2BIG;
+		if (bytes >= OOB_SPAN)
+			goto out;
+		rc = -ENOMEM;
+		if (bytes > e->lso_stage_cap) {
+			hmem_free(e->lso_stage, e->lso_stage_pinned);
+			e->lso_stage_cap = 0;
+			e->lso_stage = hmem_alloc(bytes + bytes / 2, &e->lso_stage_pinned);
+			if (!e->lso_stage)
+				goto out;
+			e->lso_stage_cap = bytes + bytes / 2;
+		}
+		size_t off = 0;
+
+		k = 0;
+		for (int i = 0; i < end; i++) {
+			if (pl[i].nseg < 2)
+				continue;
+			const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
+
+			memcpy(e->lso_stage + off, h->head + h->data_off, h->len);
+			e->lso_off[k++] = (uint32_t)off;
+			off += (h->len + 63u) & ~63u;
+			for (int s = 0; s < pl[i].nseg; s++) {
+				e->lso_seg[pl[i].first + (uint32_t)s].off = (uint32_t)off;
+				off += (rt_pkt_hdr(segs[pl[i].first + (uint32_t)s])->len + 63u) & ~63u;
+			}
+		}
+		base = e->lso_stage;
+	}
+	rc = odp_amd_cls_lso_segment_host(e->hdl, base, bytes, e->lso_off, e->lso_len, e->lso_desc, nsrc, e->lso_seg,
+					  nsegs, tab, MI_CLS_LSO_PROFILES, e->lso_st);
+	if (rc)
+		goto out;
+	for (uint32_t j = 0; !in_place && j < nsegs; j++) {
+		pkt_hdr_t *sh = rt_pkt_hdr(segs[j]);
+
+		if (e->lso_st[e->lso_seg[j].src] == MI_CLS_LSO_ST_OK)
+			memcpy(sh->head + sh->data_off, e->lso_stage + e->lso_seg[j].off, sh->len);
+	}
+	k = 0;
+	for (int i = 0; i < end; i++)
+		if (pl[i].nseg >= 2)
+			pl[i].st = e->lso_st[k++];
+	e->lso_bursts++;
+	e->lso_bounced += !in_place;
+out:
+	pthread_mutex_unlock(&e->txl);
+	return rc;
+}
+
+/* odp_pktout_send_lso (odp_packet_io.c:3253-3348) with one kernel launch for
+ * the whole call: every packet is planned on the host (mi_cls_lso_plan,
+ * _odp_lso_num_packets), the segments of the packets that need them are
+ * allocated from each source's pool (:3172-3189), one launch cuts and edits
+ * them all (_odp_lso_create_packets), and the list -- a packet's segments, or
+ * the packet itself -- goes to odp_pktout_send in order.  The list ends at the
+ * first packet without a request (opt == NULL), whose plan or allocation
+ * fails, or whose header the kernel refuses.  Returns the source packets
+ * completely sent; their originals are freed when they were segmented; a
+ * packet of which only some segments were taken counts as failed: its unsent
+ * segments are freed and its original stays with the caller (:3284-3297). */
+int odp_pktout_send_lso(odp_pktout_queue_t q, const odp_packet_t pkts[], int num, const odp_packet_lso_opt_t *opt)
+{
+	rt_pktio_t *e = get_pk(q.pktio);
+
+	if (!e || num <= 0)
+		return -1;
+	/* as odp_pktout_send: nothing is sent on a pktio that is not started --
+	 * which is every pktio where there is no GPU (odp_pktio_start fails):
+	 * no CPU segmentation stands in, said once */
+	if (e->state != ST_STARTED) {
+		if (!LSO.not_started_said)
+			RT_ERR("pktio %s: odp_pktout_send_lso on a pktio that is not started\n", e->name);
+		LSO.not_started_said = 1;
+		return -1;
+	}
+	lso_plan_t *pl = calloc((size_t)num, sizeof(*pl));
+	odp_packet_t *segs = NULL, *out = NULL;
+	uint32_t nsegs = 0, nsrc = 0;
+	int end = 0, sent = 0, ret = -1;
+
+	if (!pl)
+		return -1;
+	/* ---- plan and allocate */
+	for (end = 0; end < num; end++) {
+		const pkt_hdr_t *h = rt_pkt_hdr(pkts[end]);
+		lso_plan_t *p = &pl[end];
+		uint32_t maxp;
+		int slot;
+
+		if (opt) {
+			slot = lso_slot(opt->lso_profile);
+			p->hdr = opt->payload_offset;
+			maxp = opt->max_payload_len;
+		} else {
+			if (!(h->lso_flags & RT_LSO_REQ)) {
+				RT_ERR("no LSO options on packet %d\n", end);
+				if (end == 0)
+					goto done;   /* -1 (:3330) */
+				break;
+			}
+			slot = h->lso_prof;
+			p->hdr = odp_packet_payload_offset(pkts[end]);
+			maxp = h->lso_max_payload;
+		}
+		if (slot < 0 || !LSO.prof[slot].used || h->len > 65535u)
+			break;
+		const uint32_t proto = (uint32_t)LSO.prof[slot].param.lso_proto;
+
+		p->prof = (uint8_t)slot;
+		p->l3 = h->l3;
+		p->nseg = mi_cls_lso_plan(h->len, p->hdr, maxp, proto, p->l3, &p->pay, &p->left);
+		if (p->nseg <= 0)
+			break;
+		if (p->nseg == 1)
+			continue;
+		odp_packet_t *ns = realloc(segs, (nsegs + (uint32_t)p->nseg) * sizeof(*segs));
+
+		if (!ns)
+			break;
+		segs = ns;
+		/* the full ones, then the left-over one (:3172-3189) */
+		const int full = p->left ? p->nseg - 1 : p->nseg;
+		const odp_pool_t pool = odp_packet_pool(pkts[end]);
+		int got = odp_packet_alloc_multi(pool, p->hdr + p->pay, &segs[nsegs], full);
+
+		if (got == full && p->left) {
+			segs[nsegs + (uint32_t)full] = odp_packet_alloc(pool, p->hdr + p->left);
+			got += segs[nsegs + (uint32_t)full] != ODP_PACKET_INVALID;
+		}
+		if (got < p->nseg) {
+			if (got > 0)
+				odp_packet_free_multi(&segs[nsegs], got);
+			break;
+		}
+		p->first = nsegs;
+		if (proto == ODP_LSO_PROTO_IPV4)   /* lso_update_ipv4 sets it (:2994) */
+			for (int s = 0; s < p->nseg; s++)
+				odp_packet_l3_offset_set(segs[nsegs + (uint32_t)s], p->l3);
+		nsegs += (uint32_t)p->nseg;
+		nsrc++;
+	}
+	/* ---- one launch for every segmented packet of the call */
+	if (nsrc) {
+		const int rc = lso_launch(e, pkts, pl, end, nsrc, segs, nsegs);
+		int cut = -1;   /* the first packet whose segments are dropped */
+
+		if (rc)   /* no CPU segmentation stands in: the list ends at the first segmented packet */
+			RT_ERR("pktio %s: LSO segmentation failed (%s)\n", e->name, mi_cls_strerror(rc));
+		for (int i = 0; i < end && cut < 0; i++)
+			if (pl[i].nseg >= 2 && (rc || pl[i].st != MI_CLS_LSO_ST_OK))
+				cut = i;
+		if (cut >= 0) {
+			for (int i = cut; i < end; i++)
+				if (pl[i].nseg >= 2)
+					odp_packet_free_multi(&segs[pl[i].first], pl[i].nseg);
+			end = cut;
+		}
+	}
+	/* ---- the output list, in order */
+	uint32_t nout = 0;
+
+	for (int i = 0; i < end; i++)
+		nout += (uint32_t)pl[i].nseg;
+	ret = 0;
+	if (nout == 0)
+		goto done;
+	out = malloc(nout * sizeof(*out));
+	if (!out) {
+		for (int i = 0; i < end; i++)
+			if (pl[i].nseg >= 2)
+				odp_packet_free_multi(&segs[pl[i].first], pl[i].nseg);
+		goto done;
+	}
+	nout = 0;
+	for (int i = 0; i < end; i++) {
+		if (pl[i].nseg >= 2)
+			memcpy(&out[nout], &segs[pl[i].first], (size_t)pl[i].nseg * sizeof(*out));
+		else
+			out[nout] = pkts[i];
+		nout += (uint32_t)pl[i].nseg;
+	}
+	int r = odp_pktout_send(q, out, (int)nout);
+
+	if (r < 0)
+		r = 0;
+	uint32_t pos = 0;
+
+	for (int i = 0; i < end; i++) {
+		const uint32_t n = (uint32_t)pl[i].nseg;
+
+		if (pos + n <= (uint32_t)r && sent == i) {
+			sent++;
+			if (n >= 2)
+				odp_packet_free(pkts[i]);   /* the original (:3300) */
+		} else if (n >= 2) {
+			/* not, or only partly, taken: its unsent segments are freed */
+			const uint32_t took = (uint32_t)r > pos ? (uint32_t)r - pos : 0;
+
+			odp_packet_free_multi(&out[pos + took], (int)(n - took));
+		}
+		pos += n;
+	}
+	ret = sent;
+done:
+	free(out);
+	free(segs);
+	free(pl);
+	return ret;
+}
+
+int odp_amd_pktio_lso_stats(odp_pktio_t h, uint64_t *bursts, uint64_t *bounced)
+{
+	rt_pktio_t *e = get_pk(h);
+
+	if (!e || !bursts || !bounced)
+		return -1;
+	pthread_mutex_lock(&e->txl);
+	*bursts = e->lso_bursts;
+	*bounced = e->lso_bounced;
+	pthread_mutex_unlock(&e->txl);
+	return 0;
 }
 
 /* ============================================================ misc */

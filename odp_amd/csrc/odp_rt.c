@@ -956,6 +956,10 @@ static void pkt_init(pkt_hdr_t *h, uint32_t len)
 	h->l3 = ODP_PACKET_OFFSET_INVALID;
 	h->l4 = ODP_PACKET_OFFSET_INVALID;
 	h->tx_ck = 0;
+	h->payload_off = 0;
+	h->lso_flags = 0;
+	h->lso_prof = 0;
+	h->lso_max_payload = 0;
 	h->dst_queue = ODP_QUEUE_INVALID;
 	h->input = ODP_PKTIO_INVALID;
 	h->user_ptr = NULL;

@@ -25,6 +25,9 @@
 #define RT_PKT_HEADROOM 128
 #define RT_PKT_TAILROOM 64
 
+#define RT_LSO_REQ 1u
+#define RT_LSO_PAYLOAD_OFF 2u
+
 #define RT_ERR(...) fprintf(stderr, "odp: " __VA_ARGS__)
 
 /* common event header: packets and event vectors start with it */
@@ -63,11 +66,19 @@ typedef struct pkt_hdr {
 			 * l3/l4_chksum of packet_parser_t.flags); the GPU receive
 			 * delivery writes the block whole, this field as 0 */
 			uint16_t tx_ck;
-			uint32_t rsv1;
+			/* LSO request state (odp_packet_lso_request; reference
+			 * p.flags.lso / payload_off, payload_offset, lso_profile_idx,
+			 * lso_max_payload) in the block's reserved words: the GPU
+			 * deliveries write them as 0, so a received packet carries
+			 * none; odp_packet_alloc clears them */
+			uint16_t payload_off;
+			uint8_t lso_flags;      /* RT_LSO_REQ | RT_LSO_PAYLOAD_OFF */
+			uint8_t lso_prof;
 			odp_queue_t dst_queue;
 			odp_pktio_t input;
 			const void *user_ptr;
-			uint64_t rsv2;
+			uint32_t lso_max_payload;
+			uint32_t rsv2;
 		};
 	};
 } pkt_hdr_t;
