@@ -249,12 +249,13 @@ def _h(x):
 TX_DESC_DTYPE = np.dtype([("l3", "<u2"), ("l4", "<u2"), ("flags", "u1"), ("rsv", "u1", (3,))])
 
 
-class TxContext:
-    """A device context for pktout checksum insertion (mi_cls_chksum_insert
-    and its host entries); needs no rules."""
+class _FeatureContext:
+    """A device context of one offload (checksum insertion, parse, LSO): its
+    own stream, staging buffers and ticket ring; needs no rules."""
 
     def __init__(self, gpu: int = 0):
         self.L = lib()
+        self.gpu = gpu
         ctx = C.c_void_p()
         rc = self.L.mi_cls_ctx_create(gpu, C.byref(ctx))
         if rc:
@@ -265,6 +266,16 @@ class TxContext:
         if self.ctx:
             self.L.mi_cls_ctx_destroy(self.ctx)
             self.ctx = None
+
+    def last_launch(self):
+        info = (C.c_uint32 * 7)()
+        self.L.mi_cls_last_launch(self.ctx, info, 7)
+        return list(info)
+
+
+class TxContext(_FeatureContext):
+    """A device context for pktout checksum insertion (mi_cls_chksum_insert
+    and its host entries); needs no rules."""
 
     def insert_device(self, d_buf, d_off, d_len, d_desc, n, opt, d_done=0, stream=0):
         """On device pointers (ints), stream-ordered.  Returns the C status."""
@@ -322,23 +333,9 @@ def chksum_insert(batch, desc, opt, gpu: int = 0):
         c.close()
 
 
-class ParseContext:
+class ParseContext(_FeatureContext):
     """A device context for the parse on its own (mi_cls_parse and its host
     entries: odp_packet_parse for a batch); needs no rules."""
-
-    def __init__(self, gpu: int = 0):
-        self.L = lib()
-        self.gpu = gpu
-        ctx = C.c_void_p()
-        rc = self.L.mi_cls_ctx_create(gpu, C.byref(ctx))
-        if rc:
-            raise RuntimeError(f"mi_cls_ctx_create: {rc} ({self.L.mi_cls_strerror(rc).decode()})")
-        self.ctx = ctx
-
-    def close(self):
-        if self.ctx:
-            self.L.mi_cls_ctx_destroy(self.ctx)
-            self.ctx = None
 
     def parse_device(self, d_buf, d_off, d_len, n, proto, last_layer, chksums, d_out, stream=0):
         """On device pointers (ints), stream-ordered.  Returns the C status."""
@@ -389,11 +386,6 @@ class ParseContext:
         if rc != 0:
             raise RuntimeError(f"mi_cls_parse_host_wait: {rc}")
 
-    def last_launch(self):
-        info = (C.c_uint32 * 7)()
-        self.L.mi_cls_last_launch(self.ctx, info, 7)
-        return list(info)
-
 
 # LSO (include/mi_cls.h): odp_lso_protocol_t / odp_lso_modify_t values, the
 # per-source descriptor, the segment table entry, st[] values
@@ -442,23 +434,9 @@ def lso_plan(length, hdr_len, max_payload, proto, l3=LSO_L3_INVALID):
     return (rc, pay.value, left.value) if rc > 0 else (rc, 0, 0)
 
 
-class LsoContext:
+class LsoContext(_FeatureContext):
     """A device context for the LSO segmentation (mi_cls_lso_segment and its
     host entries); needs no rules."""
-
-    def __init__(self, gpu: int = 0):
-        self.L = lib()
-        self.gpu = gpu
-        ctx = C.c_void_p()
-        rc = self.L.mi_cls_ctx_create(gpu, C.byref(ctx))
-        if rc:
-            raise RuntimeError(f"mi_cls_ctx_create: {rc} ({self.L.mi_cls_strerror(rc).decode()})")
-        self.ctx = ctx
-
-    def close(self):
-        if self.ctx:
-            self.L.mi_cls_ctx_destroy(self.ctx)
-            self.ctx = None
 
     plan = staticmethod(lso_plan)
 
@@ -506,11 +484,6 @@ class LsoContext:
                 rc = self.L.mi_cls_lso_segment_host_wait(self.ctx, t.value)
             return rc
         return self.L.mi_cls_lso_segment_host(*args)
-
-    def last_launch(self):
-        info = (C.c_uint32 * 7)()
-        self.L.mi_cls_last_launch(self.ctx, info, 7)
-        return list(info)
 
 
 class Classifier:

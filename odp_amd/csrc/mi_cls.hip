@@ -613,11 +613,10 @@ extern "C" int mi_cls_classify(mi_cls_ctx_t *c, const uint8_t *pkts, const uint3
 	return 0;
 }
 
-// Stage frames [lo, hi) of a host batch (descriptors rebased by lo) through
-// the context's device buffers on its own stream and launch the kernel; the
-// records go to `out` (any host memory) or, when out is NULL, to the
-// context's pinned record buffer h_out (multi-GPU: no host wait per device).
-// Nothing is waited for here.
+// ------------------------------------------------------------- host batches
+// The steps classify, checksum insertion, parse and LSO share (DESIGN.md,
+// "The host-batch contract"), each written once.
+
 // Device address of page-locked host memory (hipHostMalloc /
 // hipHostRegister), NULL for pageable memory.
 // Page-locked allocations of mi_cls_host_alloc: start -> (bytes, device
@@ -656,60 +655,48 @@ static const void *dev_view(const void *p)
 	return dev_view_slow(p);
 }
 
-static int stage_bufs(mi_cls_ctx_t *c, size_t need, uint32_t n);
-
-// `lim` is the size of the caller's buffer at `pkts`: the zero-copy path is
-// taken only when every frame's last 16-B piece (the kernel reads frames in
-// 16-B pieces from their start) lies inside it; otherwise the frames are
-// staged into the padded device buffer.
-static int host_launch(mi_cls_ctx_t *c, const uint8_t *pkts, size_t lo, size_t hi, size_t lim,
-		       const uint32_t *off, const uint16_t *len, uint32_t n, mi_cls_result_t *out)
+// Each pointer replaced by its device view, in order, up to the first one
+// that is pageable: true when all of them are page-locked.
+template <typename T> static bool dev_views(T *&p)
 {
-	HIP_OK(set_device(c->device));
-	if (!c->stream)
-		HIP_OK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-	// Zero copy: frames and descriptors in page-locked memory are read by the
-	// kernel in place over the host link -- only the header windows it
-	// touches cross it, not whole frames -- and the records are written
-	// straight into page-locked `out`.
-	const void *zp = dev_view(pkts), *zo = zp ? dev_view(off) : nullptr;
-	const void *zl = zo ? dev_view(len) : nullptr;
-	for (uint32_t i = 0; zl && i < n; ++i)
+	const void *d = dev_view(p);
+	return d ? (p = (T *)d, true) : false;
+}
+template <typename T, typename... U> static bool dev_views(T *&p, U *&...more)
+{
+	return dev_views(p) && dev_views(more...);
+}
+
+// What an entry point answers without a context
+static int no_ctx(void)
+{
+	return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
+}
+
+// Every frame lies inside the `bytes` of its buffer
+static bool frames_inside(const uint32_t *off, const uint16_t *len, uint32_t n, size_t bytes)
+{
+	for (uint32_t i = 0; i < n; ++i)
+		if ((size_t)off[i] + len[i] > bytes)
+			return false;
+	return true;
+}
+
+// The zero-copy condition: the kernels read a frame in 16-B pieces from its
+// start, and every frame's last piece lies inside the caller's `lim` bytes
+// (a batch that fails it is staged into the padded device buffer)
+static bool frames_padded_inside(const uint32_t *off, const uint16_t *len, uint32_t n, size_t lim)
+{
+	for (uint32_t i = 0; i < n; ++i)
 		if ((size_t)off[i] + (((size_t)len[i] + 15u) & ~(size_t)15u) > lim)
-			zl = nullptr;
-	if (zl) {
-		mi_cls_result_t *o = out ? out : n <= c->n_cap ? c->h_out : nullptr;
-		const void *zr = o ? dev_view(o) : nullptr;
-		if (zr)   // descriptors keep their offsets relative to `pkts`
-			return mi_cls_classify(c, (const uint8_t *)zp, (const uint32_t *)zo,
-					       (const uint16_t *)zl, n, (mi_cls_result_t *)zr, c->stream);
-	}
-	const size_t bytes = hi - lo;
-	int rc = stage_bufs(c, bytes + 64, n);
-	if (rc)
-		return rc;
-	hipStream_t s = c->stream;
-	const uint32_t *doff = off;
-	if (lo) {
-		for (uint32_t i = 0; i < n; ++i)
-			c->h_off[i] = off[i] - (uint32_t)lo;
-		doff = c->h_off;
-	}
-	HIP_OK(hipMemcpyAsync(c->d_pk, pkts + lo, bytes, hipMemcpyHostToDevice, s));
-	HIP_OK(hipMemcpyAsync(c->d_off, doff, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-	HIP_OK(hipMemcpyAsync(c->d_len, len, n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-	rc = mi_cls_classify(c, c->d_pk, c->d_off, c->d_len, n, c->d_out, s);
-	if (rc)
-		return rc;
-	HIP_OK(hipMemcpyAsync(out ? out : c->h_out, c->d_out, n * sizeof(mi_cls_result_t),
-			      hipMemcpyDeviceToHost, s));
-	return 0;
+			return false;
+	return true;
 }
 
 // The context's device staging buffers for a host batch of `need` frame bytes
-// (padding included) and n packets, grown geometrically and kept across
-// calls: d_pk, d_off, d_len, d_out (16 B per packet: records, or the
-// transmit descriptors and done bytes) and the pinned h_off / h_out.
+// (padding included) and n entries, grown geometrically and kept across
+// calls: d_pk, d_off, d_len, d_out (16 B per entry: records, or what the
+// stg_* accessors below place there) and the pinned h_off / h_out.
 static int stage_bufs(mi_cls_ctx_t *c, size_t need, uint32_t n)
 {
 	if ((need > c->pk_cap || n > c->n_cap) && c->submitted)
@@ -746,32 +733,42 @@ static int stage_bufs(mi_cls_ctx_t *c, size_t need, uint32_t n)
 	return 0;
 }
 
-// Host-memory batch: stage through device buffers owned by the context on its
-// own stream (grown geometrically, kept across calls), classify, copy back.
-extern "C" int mi_cls_classify_host(mi_cls_ctx_t *c, const uint8_t *pkts, size_t bytes,
-				    const uint32_t *off, const uint16_t *len, uint32_t n,
-				    mi_cls_result_t *out)
+// Stage a batch up on the context's stream: staging buffers for `room` frame
+// bytes (+ 64 of padding) and `entries` per-entry slots, then the `bytes` at
+// `frames` to d_pk, the n offsets (less `rebase`, through h_off) to d_off and
+// the n lengths to d_len.
+static int stage_up(mi_cls_ctx_t *c, const uint8_t *frames, size_t bytes, size_t room, const uint32_t *off,
+		    const uint16_t *len, uint32_t n, uint32_t entries, size_t rebase = 0)
 {
-	if (!c || !c->loaded)
-		return -EINVAL;
-	if (n == 0)
-		return 0;
-	if (!pkts || !off || !len || !out)
-		return -EINVAL;
-	// every frame must lie inside the staged bytes (the kernel reads up to
-	// the next 16-byte boundary after a frame; the staging buffer is padded)
-	for (uint32_t i = 0; i < n; ++i)
-		if ((size_t)off[i] + len[i] > bytes)
-			return -EINVAL;
-	int rc = host_launch(c, pkts, 0, bytes, bytes, off, len, n, out);
+	const int rc = stage_bufs(c, room + 64, entries);
 	if (rc)
 		return rc;
-	HIP_OK(hipStreamSynchronize(c->stream));
+	if (rebase) {
+		for (uint32_t i = 0; i < n; ++i)
+			c->h_off[i] = off[i] - (uint32_t)rebase;
+		off = c->h_off;
+	}
+	HIP_OK(hipMemcpyAsync(c->d_pk, frames, bytes, hipMemcpyHostToDevice, c->stream));
+	HIP_OK(hipMemcpyAsync(c->d_off, off, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	HIP_OK(hipMemcpyAsync(c->d_len, len, n * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
 	return 0;
 }
 
-// Submit a host batch without waiting (pipelined receive): the caller keeps
-// pkts / off / len / out untouched until mi_cls_classify_host_wait(ticket).
+// What the staged forms of checksum insertion and LSO place in the staging
+// buffers beside frames, offsets and lengths (d_out has 16 B, d_len 2 B for
+// each of n_cap entries).  Checksum, n entries: d_out = n_cap descriptors
+// (8 B), then the done bytes.  LSO, 2n + nsegs entries: d_out = n descriptors
+// (16 B), then the segment table (8 B each); d_len = n lengths, then n status
+// bytes; d_pk = the sources, then, from a 256-B boundary, the destination
+// (the same bytes when src == dst).
+static mi_cls_tx_desc_t *stg_tx_desc(const mi_cls_ctx_t *c) { return (mi_cls_tx_desc_t *)c->d_out; }
+static uint8_t *stg_tx_done(const mi_cls_ctx_t *c) { return (uint8_t *)(stg_tx_desc(c) + c->n_cap); }
+static mi_cls_lso_desc_t *stg_lso_desc(const mi_cls_ctx_t *c) { return (mi_cls_lso_desc_t *)c->d_out; }
+static mi_cls_lso_seg_t *stg_lso_seg(const mi_cls_ctx_t *c, uint32_t n) { return (mi_cls_lso_seg_t *)(c->d_out + n); }
+static uint8_t *stg_lso_st(const mi_cls_ctx_t *c, uint32_t n) { return (uint8_t *)(c->d_len + n); }
+static size_t stg_lso_dst(bool same, size_t src_bytes) { return same ? 0 : (src_bytes + 255u) & ~(size_t)255u; }
+
+// ---- the ticket ring: tickets numbered from 1, completion events in 8 slots
 // Wait for ticket t (its slot still holds it): nothing if it was seen
 // complete before, else a query, then a blocking wait only if it runs.
 static int ring_wait(mi_cls_ctx_t *c, uint64_t t)
@@ -786,17 +783,106 @@ static int ring_wait(mi_cls_ctx_t *c, uint64_t t)
 	return 0;
 }
 
-// Ring slot t % 8 for ticket t: ticket t - 8 must be complete first.  A
-// ticket already waited for needs no runtime call; otherwise a query, and a
-// blocking wait only while it still runs.
-static int ring_slot(mi_cls_ctx_t *c, uint64_t t)
+// Begin the context's next ticket t: its device current and its ring slot
+// t % 8 free, that is ticket t - 8 complete (the submitter may now reuse the
+// slot's own arrays).  A ticket already waited for needs no runtime call;
+// otherwise a query, and a blocking wait only while it still runs.
+static int ticket_begin(mi_cls_ctx_t *c, uint64_t *t)
 {
-	hipEvent_t *ev = &c->ev[t % 8];
-	if (!*ev)
-		return hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess ? 0 : -EIO;
-	return ring_wait(c, t - 8);
+	*t = c->submitted + 1;
+	HIP_OK(set_device(c->device));
+	return ring_wait(c, *t - 8);
 }
 
+// Commit ticket t: its event after what the submitter queued on stream `s`
+static int ticket_commit(mi_cls_ctx_t *c, uint64_t t, hipStream_t s, uint64_t *ticket)
+{
+	HIP_OK(hipEventRecord(c->ev[t % 8], s));
+	c->submitted = t;
+	*ticket = t;
+	return 0;
+}
+
+// The two forms of a checked host batch over its feature's `launch` (which
+// queues the batch on the context's stream): the _host form (ticket NULL)
+// waits for the stream, the _host_submit form commits a ticket.
+template <typename L> static int host_run(mi_cls_ctx_t *c, uint64_t *ticket, L launch)
+{
+	uint64_t t = 0;
+	int rc = ticket ? ticket_begin(c, &t) : 0;
+	if (!rc)
+		rc = launch();
+	if (rc)
+		return rc;
+	if (ticket)
+		return ticket_commit(c, t, c->stream, ticket);
+	HIP_OK(hipStreamSynchronize(c->stream));
+	return 0;
+}
+
+// Wait for a ticket of the ring (every feature's _host_wait)
+static int host_wait(mi_cls_ctx_t *c, uint64_t ticket)
+{
+	if (ticket > c->submitted)
+		return -EINVAL;
+	if (ticket == 0 || ticket + 8 <= c->submitted)
+		return 0;   // nothing submitted, or its slot was reused (waited for then)
+	HIP_OK(set_device(c->device));
+	return ring_wait(c, ticket);
+}
+
+// ------------------------------------------------------- classify host batch
+// Frames [lo, hi) of a host batch (the group entries give a slice) on the
+// context's stream, nothing waited for: in place when frames, descriptors
+// and records are page-locked and frames_padded_inside(lim), `lim` being the
+// size of the caller's buffer at `pkts` -- only the header windows the
+// kernel touches cross the host link then, not whole frames.  Otherwise
+// staged, the descriptors rebased by lo.  The records go to `out` (any host
+// memory) or, when out is NULL, to the context's pinned record buffer h_out
+// (multi-GPU: no host wait per device).
+static int host_launch(mi_cls_ctx_t *c, const uint8_t *pkts, size_t lo, size_t hi, size_t lim,
+		       const uint32_t *off, const uint16_t *len, uint32_t n, mi_cls_result_t *out)
+{
+	HIP_OK(set_device(c->device));
+	const uint8_t *zp = pkts;
+	const uint32_t *zo = off;
+	const uint16_t *zl = len;
+	mi_cls_result_t *zr = out ? out : n <= c->n_cap ? c->h_out : nullptr;
+	if (dev_views(zp, zo, zl) && frames_padded_inside(off, len, n, lim) && zr && dev_views(zr))
+		return mi_cls_classify(c, zp, zo, zl, n, zr, c->stream);   // offsets stay relative to `pkts`
+	int rc = stage_up(c, pkts + lo, hi - lo, hi - lo, off, len, n, n, lo);
+	if (rc)
+		return rc;
+	rc = mi_cls_classify(c, c->d_pk, c->d_off, c->d_len, n, c->d_out, c->stream);
+	if (rc)
+		return rc;
+	HIP_OK(hipMemcpyAsync(out ? out : c->h_out, c->d_out, n * sizeof(mi_cls_result_t),
+			      hipMemcpyDeviceToHost, c->stream));
+	return 0;
+}
+
+static int classify_host_check(const mi_cls_ctx_t *c, const uint8_t *pkts, size_t bytes, const uint32_t *off,
+			       const uint16_t *len, uint32_t n, const mi_cls_result_t *out)
+{
+	if (!c || !c->loaded)
+		return -EINVAL;
+	if (n == 0)
+		return 0;
+	return pkts && off && len && out && frames_inside(off, len, n, bytes) ? 0 : -EINVAL;
+}
+
+extern "C" int mi_cls_classify_host(mi_cls_ctx_t *c, const uint8_t *pkts, size_t bytes,
+				    const uint32_t *off, const uint16_t *len, uint32_t n,
+				    mi_cls_result_t *out)
+{
+	const int rc = classify_host_check(c, pkts, bytes, off, len, n, out);
+	if (rc || n == 0)
+		return rc;
+	return host_run(c, nullptr, [&] { return host_launch(c, pkts, 0, bytes, bytes, off, len, n, out); });
+}
+
+// Submit a host batch without waiting (pipelined receive): the caller keeps
+// pkts / off / len / out untouched until mi_cls_classify_host_wait(ticket).
 extern "C" int mi_cls_classify_host_submit(mi_cls_ctx_t *c, const uint8_t *pkts, size_t bytes,
 					   const uint32_t *off, const uint16_t *len, uint32_t n,
 					   mi_cls_result_t *out, uint64_t *ticket)
@@ -804,25 +890,10 @@ extern "C" int mi_cls_classify_host_submit(mi_cls_ctx_t *c, const uint8_t *pkts,
 	if (!c || !c->loaded || !ticket)
 		return -EINVAL;
 	*ticket = 0;
-	if (n == 0)
-		return 0;
-	if (!pkts || !off || !len || !out)
-		return -EINVAL;
-	for (uint32_t i = 0; i < n; ++i)
-		if ((size_t)off[i] + len[i] > bytes)
-			return -EINVAL;
-	const uint64_t t = c->submitted + 1;
-	hipEvent_t *ev = &c->ev[t % 8];
-	HIP_OK(set_device(c->device));
-	if (ring_slot(c, t))
-		return -EIO;
-	int rc = host_launch(c, pkts, 0, bytes, bytes, off, len, n, out);
-	if (rc)
+	const int rc = classify_host_check(c, pkts, bytes, off, len, n, out);
+	if (rc || n == 0)
 		return rc;
-	HIP_OK(hipEventRecord(*ev, c->stream));
-	c->submitted = t;
-	*ticket = t;
-	return 0;
+	return host_run(c, ticket, [&] { return host_launch(c, pkts, 0, bytes, bytes, off, len, n, out); });
 }
 
 extern "C" int mi_cls_host_mapped(const void *p)
@@ -853,18 +924,15 @@ extern "C" int mi_cls_deliver_submit(mi_cls_ctx_t *c, const mi_cls_dlv_args_t *a
 			if (a->dlv[j].qid != 0xFFu)
 				return -E2BIG;
 	}
-	HIP_OK(set_device(c->device));
-	const uint64_t t = c->submitted + 1;
-	if (ring_slot(c, t))
-		return -EIO;
-	const unsigned grid = (a->n + 15u) / 16u + 1u;
-	int rc = mi_cls_launch_deliver(grid, c->dstream, *a);
+	uint64_t t;
+	int rc = ticket_begin(c, &t);
 	if (rc)
 		return rc;
-	HIP_OK(hipEventRecord(c->ev[t % 8], c->dstream));
-	c->submitted = t;
-	*ticket = t;
-	return 0;
+	const unsigned grid = (a->n + 15u) / 16u + 1u;
+	rc = mi_cls_launch_deliver(grid, c->dstream, *a);
+	if (rc)
+		return rc;
+	return ticket_commit(c, t, c->dstream, ticket);
 }
 
 // The receive chain of one burst (mi_cls.h): its classification (zero copy:
@@ -888,13 +956,12 @@ extern "C" int mi_cls_rx_chain_submit(mi_cls_ctx_t *c, const uint8_t *pkts, size
 	    (a->stage && !a->pk))
 		return -EINVAL;
 	// the descriptors stay inside the batch (the stage kernel checks its own)
-	for (uint32_t i = 0; !a->stage && i < a->n; ++i)
-		if ((size_t)a->soff[i] + (((size_t)a->slen[i] + 15u) & ~(size_t)15u) > bytes)
-			return -EINVAL;
-	HIP_OK(set_device(c->device));
-	const uint64_t t = c->submitted + 1;
-	if (ring_slot(c, t))
-		return -EIO;
+	if (!a->stage && !frames_padded_inside(a->soff, a->slen, a->n, bytes))
+		return -EINVAL;
+	uint64_t t;
+	int rc = ticket_begin(c, &t);
+	if (rc)
+		return rc;
 	// the whole chain on one of the context's two streams, by ticket
 	// parity: a burst's kernels are ordered by their stream (no events
 	// between them: each event record and stream wait costs the host 1.5-4
@@ -912,7 +979,7 @@ extern "C" int mi_cls_rx_chain_submit(mi_cls_ctx_t *c, const uint8_t *pkts, size
 	// buffer, not the caller's live table: the caller may rewrite that table
 	// (a control-plane change) while this asynchronous copy is still queued,
 	// and the burst must run on the table it was submitted with.  The slot's
-	// previous chain, and so its copy, has completed (ring_slot).
+	// previous chain, and so its copy, has completed (ticket_begin).
 	if (c->tab_src[t % 8] != a->tab || c->tab_stamp[t % 8] != a->tab->stamp) {
 		c->tab_src[t % 8] = nullptr;
 		mi_cls_rxtab_t *snap = c->h_tab + (t % 8);
@@ -921,7 +988,7 @@ extern "C" int mi_cls_rx_chain_submit(mi_cls_ctx_t *c, const uint8_t *pkts, size
 		c->tab_src[t % 8] = a->tab;
 		c->tab_stamp[t % 8] = snap->stamp;
 	}
-	int rc = a->stage ? mi_cls_launch_rx_stage(xs, *a, d, bytes, false) : 0;
+	rc = a->stage ? mi_cls_launch_rx_stage(xs, *a, d, bytes, false) : 0;
 	if (rc)
 		return rc;
 	rc = mi_cls_classify(c, pkts, a->soff, a->slen, a->n, d.res, xs);
@@ -930,33 +997,37 @@ extern "C" int mi_cls_rx_chain_submit(mi_cls_ctx_t *c, const uint8_t *pkts, size
 	rc = mi_cls_launch_rx_chain(xs, *a, d, false);
 	if (rc)
 		return rc;
-	HIP_OK(hipEventRecord(c->ev[t % 8], xs));
-	c->submitted = t;
-	*ticket = t;
-	return 0;
+	return ticket_commit(c, t, xs, ticket);
 }
 
 extern "C" int mi_cls_classify_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
 {
-	if (!c || ticket > c->submitted)
-		return -EINVAL;
-	if (ticket == 0 || ticket + 8 <= c->submitted)
-		return 0;   // nothing submitted, or its slot was reused (waited for then)
-	HIP_OK(set_device(c->device));
-	return ring_wait(c, ticket);
+	return c ? host_wait(c, ticket) : -EINVAL;
+}
+
+// The features below answer a missing context with no_ctx()
+static int feature_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
+{
+	return c ? host_wait(c, ticket) : no_ctx();
 }
 
 // ------------------------------------------------- pktout checksum insertion
+// The context first, then the batch (an empty one is no error)
+static int tx_check(const mi_cls_ctx_t *c, const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
+		    const mi_cls_tx_desc_t *desc, uint32_t n)
+{
+	if (!c)
+		return no_ctx();
+	return n == 0 || (pkts && off && len && desc && ((uintptr_t)desc & 7u) == 0) ? 0 : -EINVAL;
+}
+
 extern "C" int mi_cls_chksum_insert(mi_cls_ctx_t *c, uint8_t *pkts, const uint32_t *off,
 				    const uint16_t *len, const mi_cls_tx_desc_t *desc, uint32_t n,
 				    uint64_t pktout_opt, uint8_t *done, void *stream)
 {
-	if (!c)
-		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
-	if (n == 0)
-		return 0;
-	if (!pkts || !off || !len || !desc || ((uintptr_t)desc & 7u) != 0)
-		return -EINVAL;
+	const int bad = tx_check(c, pkts, off, len, desc, n);
+	if (bad || n == 0)
+		return bad;
 	HIP_OK(set_device(c->device));
 	TxArgs a;
 	a.pkts = pkts;
@@ -979,35 +1050,26 @@ extern "C" int mi_cls_chksum_insert(mi_cls_ctx_t *c, uint8_t *pkts, const uint32
 }
 
 // A host batch on the context's stream, nothing waited for: in place when
-// everything is page-locked and every frame's 16-B rounding lies inside the
-// buffer, else through the staging buffers (the frames copied back whole:
-// only checksum fields differ).
+// everything is page-locked (`done` too, where given) and
+// frames_padded_inside(bytes), else through the staging buffers (the frames
+// copied back whole: only checksum fields differ).
 static int tx_host_launch(mi_cls_ctx_t *c, uint8_t *pkts, size_t bytes, const uint32_t *off,
 			  const uint16_t *len, const mi_cls_tx_desc_t *desc, uint32_t n, uint64_t opt,
 			  uint8_t *done)
 {
 	HIP_OK(set_device(c->device));
-	const void *zp = dev_view(pkts), *zo = zp ? dev_view(off) : nullptr;
-	const void *zl = zo ? dev_view(len) : nullptr, *zd = zl ? dev_view(desc) : nullptr;
-	const void *zn = zd && done ? dev_view(done) : nullptr;
-	if (done && !zn)
-		zd = nullptr;
-	for (uint32_t i = 0; zd && i < n; ++i)
-		if ((size_t)off[i] + (((size_t)len[i] + 15u) & ~(size_t)15u) > bytes)
-			zd = nullptr;
-	if (zd)
-		return mi_cls_chksum_insert(c, (uint8_t *)zp, (const uint32_t *)zo, (const uint16_t *)zl,
-					    (const mi_cls_tx_desc_t *)zd, n, opt, (uint8_t *)zn, c->stream);
-	int rc = stage_bufs(c, bytes + 64, n);
+	uint8_t *zp = pkts, *zn = done;
+	const uint32_t *zo = off;
+	const uint16_t *zl = len;
+	const mi_cls_tx_desc_t *zd = desc;
+	if (dev_views(zp, zo, zl, zd) && (!done || dev_views(zn)) && frames_padded_inside(off, len, n, bytes))
+		return mi_cls_chksum_insert(c, zp, zo, zl, zd, n, opt, zn, c->stream);
+	int rc = stage_up(c, pkts, bytes, bytes, off, len, n, n);
 	if (rc)
 		return rc;
 	hipStream_t s = c->stream;
-	// d_out (16 B per packet): the descriptors, then the done bytes
-	mi_cls_tx_desc_t *d_desc = (mi_cls_tx_desc_t *)c->d_out;
-	uint8_t *d_done = (uint8_t *)c->d_out + (size_t)c->n_cap * sizeof(mi_cls_tx_desc_t);
-	HIP_OK(hipMemcpyAsync(c->d_pk, pkts, bytes, hipMemcpyHostToDevice, s));
-	HIP_OK(hipMemcpyAsync(c->d_off, off, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-	HIP_OK(hipMemcpyAsync(c->d_len, len, n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+	mi_cls_tx_desc_t *d_desc = stg_tx_desc(c);
+	uint8_t *d_done = stg_tx_done(c);
 	HIP_OK(hipMemcpyAsync(d_desc, desc, n * sizeof(mi_cls_tx_desc_t), hipMemcpyHostToDevice, s));
 	rc = mi_cls_chksum_insert(c, c->d_pk, c->d_off, c->d_len, d_desc, n, opt, done ? d_done : nullptr, s);
 	if (rc)
@@ -1021,16 +1083,8 @@ static int tx_host_launch(mi_cls_ctx_t *c, uint8_t *pkts, size_t bytes, const ui
 static int tx_host_check(mi_cls_ctx_t *c, const uint8_t *pkts, size_t bytes, const uint32_t *off,
 			 const uint16_t *len, const mi_cls_tx_desc_t *desc, uint32_t n)
 {
-	if (!c)
-		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
-	if (n == 0)
-		return 0;
-	if (!pkts || !off || !len || !desc || ((uintptr_t)desc & 7u) != 0)
-		return -EINVAL;
-	for (uint32_t i = 0; i < n; ++i)
-		if ((size_t)off[i] + len[i] > bytes)
-			return -EINVAL;
-	return 0;
+	const int rc = tx_check(c, pkts, off, len, desc, n);
+	return rc || n == 0 || frames_inside(off, len, n, bytes) ? rc : -EINVAL;
 }
 
 extern "C" int mi_cls_chksum_insert_host(mi_cls_ctx_t *c, uint8_t *pkts, size_t bytes,
@@ -1038,14 +1092,10 @@ extern "C" int mi_cls_chksum_insert_host(mi_cls_ctx_t *c, uint8_t *pkts, size_t 
 					 const mi_cls_tx_desc_t *desc, uint32_t n, uint64_t opt,
 					 uint8_t *done)
 {
-	int rc = tx_host_check(c, pkts, bytes, off, len, desc, n);
+	const int rc = tx_host_check(c, pkts, bytes, off, len, desc, n);
 	if (rc || n == 0)
 		return rc;
-	rc = tx_host_launch(c, pkts, bytes, off, len, desc, n, opt, done);
-	if (rc)
-		return rc;
-	HIP_OK(hipStreamSynchronize(c->stream));
-	return 0;
+	return host_run(c, nullptr, [&] { return tx_host_launch(c, pkts, bytes, off, len, desc, n, opt, done); });
 }
 
 extern "C" int mi_cls_chksum_insert_host_submit(mi_cls_ctx_t *c, uint8_t *pkts, size_t bytes,
@@ -1056,27 +1106,15 @@ extern "C" int mi_cls_chksum_insert_host_submit(mi_cls_ctx_t *c, uint8_t *pkts, 
 	if (!ticket)
 		return -EINVAL;
 	*ticket = 0;
-	int rc = tx_host_check(c, pkts, bytes, off, len, desc, n);
+	const int rc = tx_host_check(c, pkts, bytes, off, len, desc, n);
 	if (rc || n == 0)
 		return rc;
-	const uint64_t t = c->submitted + 1;
-	HIP_OK(set_device(c->device));
-	if (ring_slot(c, t))
-		return -EIO;
-	rc = tx_host_launch(c, pkts, bytes, off, len, desc, n, opt, done);
-	if (rc)
-		return rc;
-	HIP_OK(hipEventRecord(c->ev[t % 8], c->stream));
-	c->submitted = t;
-	*ticket = t;
-	return 0;
+	return host_run(c, ticket, [&] { return tx_host_launch(c, pkts, bytes, off, len, desc, n, opt, done); });
 }
 
 extern "C" int mi_cls_chksum_insert_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
 {
-	if (!c)
-		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
-	return mi_cls_classify_host_wait(c, ticket);
+	return feature_host_wait(c, ticket);
 }
 
 // ------------------------------------------------------ the parse on its own
@@ -1087,7 +1125,7 @@ static int parse_check(const mi_cls_ctx_t *c, const mi_cls_parse_param_t *pp)
 	    pp->last_layer < MI_CLS_LAYER_L2 || pp->last_layer > MI_CLS_LAYER_ALL)
 		return -EINVAL;
 	if (!c)
-		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
+		return no_ctx();
 	return 0;
 }
 
@@ -1138,32 +1176,26 @@ extern "C" int mi_cls_parse(mi_cls_ctx_t *c, const uint8_t *pkts, const uint32_t
 }
 
 // A host batch on the context's stream, nothing waited for: in place when
-// everything is page-locked and every frame's 16-B rounding lies inside the
-// buffer, else through the staging buffers (only the records come back).
+// everything is page-locked, frames_padded_inside(bytes) and the records are
+// 16-B aligned, else through the staging buffers (only the records come back).
 static int parse_host_launch(mi_cls_ctx_t *c, const uint8_t *pkts, size_t bytes, const uint32_t *off,
 			     const uint16_t *len, uint32_t n, const mi_cls_parse_param_t *pp,
 			     mi_cls_result_t *out)
 {
 	HIP_OK(set_device(c->device));
-	const void *zp = dev_view(pkts), *zo = zp ? dev_view(off) : nullptr;
-	const void *zl = zo ? dev_view(len) : nullptr, *zr = zl ? dev_view(out) : nullptr;
-	for (uint32_t i = 0; zr && i < n; ++i)
-		if ((size_t)off[i] + (((size_t)len[i] + 15u) & ~(size_t)15u) > bytes)
-			zr = nullptr;
-	if (zr && ((uintptr_t)zr & 15u) == 0)
-		return mi_cls_parse(c, (const uint8_t *)zp, (const uint32_t *)zo, (const uint16_t *)zl, n, pp,
-				    (mi_cls_result_t *)zr, c->stream);
-	int rc = stage_bufs(c, bytes + 64, n);
+	const uint8_t *zp = pkts;
+	const uint32_t *zo = off;
+	const uint16_t *zl = len;
+	mi_cls_result_t *zr = out;
+	if (dev_views(zp, zo, zl, zr) && frames_padded_inside(off, len, n, bytes) && ((uintptr_t)zr & 15u) == 0)
+		return mi_cls_parse(c, zp, zo, zl, n, pp, zr, c->stream);
+	int rc = stage_up(c, pkts, bytes, bytes, off, len, n, n);
 	if (rc)
 		return rc;
-	hipStream_t s = c->stream;
-	HIP_OK(hipMemcpyAsync(c->d_pk, pkts, bytes, hipMemcpyHostToDevice, s));
-	HIP_OK(hipMemcpyAsync(c->d_off, off, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-	HIP_OK(hipMemcpyAsync(c->d_len, len, n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-	rc = mi_cls_parse(c, c->d_pk, c->d_off, c->d_len, n, pp, c->d_out, s);
+	rc = mi_cls_parse(c, c->d_pk, c->d_off, c->d_len, n, pp, c->d_out, c->stream);
 	if (rc)
 		return rc;
-	HIP_OK(hipMemcpyAsync(out, c->d_out, n * sizeof(mi_cls_result_t), hipMemcpyDeviceToHost, s));
+	HIP_OK(hipMemcpyAsync(out, c->d_out, n * sizeof(mi_cls_result_t), hipMemcpyDeviceToHost, c->stream));
 	return 0;
 }
 
@@ -1171,29 +1203,20 @@ static int parse_host_check(const mi_cls_ctx_t *c, const uint8_t *pkts, size_t b
 			    const uint16_t *len, uint32_t n, const mi_cls_parse_param_t *pp,
 			    const mi_cls_result_t *out)
 {
-	int rc = parse_check(c, pp);
+	const int rc = parse_check(c, pp);
 	if (rc || n == 0)
 		return rc;
-	if (!pkts || !off || !len || !out)
-		return -EINVAL;
-	for (uint32_t i = 0; i < n; ++i)
-		if ((size_t)off[i] + len[i] > bytes)
-			return -EINVAL;
-	return 0;
+	return pkts && off && len && out && frames_inside(off, len, n, bytes) ? 0 : -EINVAL;
 }
 
 extern "C" int mi_cls_parse_host(mi_cls_ctx_t *c, const uint8_t *pkts, size_t bytes, const uint32_t *off,
 				 const uint16_t *len, uint32_t n, const mi_cls_parse_param_t *pp,
 				 mi_cls_result_t *out)
 {
-	int rc = parse_host_check(c, pkts, bytes, off, len, n, pp, out);
+	const int rc = parse_host_check(c, pkts, bytes, off, len, n, pp, out);
 	if (rc || n == 0)
 		return rc;
-	rc = parse_host_launch(c, pkts, bytes, off, len, n, pp, out);
-	if (rc)
-		return rc;
-	HIP_OK(hipStreamSynchronize(c->stream));
-	return 0;
+	return host_run(c, nullptr, [&] { return parse_host_launch(c, pkts, bytes, off, len, n, pp, out); });
 }
 
 extern "C" int mi_cls_parse_host_submit(mi_cls_ctx_t *c, const uint8_t *pkts, size_t bytes,
@@ -1204,27 +1227,15 @@ extern "C" int mi_cls_parse_host_submit(mi_cls_ctx_t *c, const uint8_t *pkts, si
 	if (!ticket)
 		return -EINVAL;
 	*ticket = 0;
-	int rc = parse_host_check(c, pkts, bytes, off, len, n, pp, out);
+	const int rc = parse_host_check(c, pkts, bytes, off, len, n, pp, out);
 	if (rc || n == 0)
 		return rc;
-	const uint64_t t = c->submitted + 1;
-	HIP_OK(set_device(c->device));
-	if (ring_slot(c, t))
-		return -EIO;
-	rc = parse_host_launch(c, pkts, bytes, off, len, n, pp, out);
-	if (rc)
-		return rc;
-	HIP_OK(hipEventRecord(c->ev[t % 8], c->stream));
-	c->submitted = t;
-	*ticket = t;
-	return 0;
+	return host_run(c, ticket, [&] { return parse_host_launch(c, pkts, bytes, off, len, n, pp, out); });
 }
 
 extern "C" int mi_cls_parse_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
 {
-	if (!c)
-		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
-	return mi_cls_classify_host_wait(c, ticket);
+	return feature_host_wait(c, ticket);
 }
 
 // ------------------------------------------------------------------------ LSO
@@ -1300,7 +1311,7 @@ extern "C" int mi_cls_lso_segment(mi_cls_ctx_t *c, const uint8_t *src, const uin
 			return rc;
 	}
 	if (!c)
-		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
+		return no_ctx();
 	if (n == 0 || nsegs == 0)
 		return 0;
 	if (!src || !off || !len || !desc || !dst || !seg || !st || ((uintptr_t)desc & 15u) != 0 ||
@@ -1356,17 +1367,19 @@ static int lso_host_check(const mi_cls_ctx_t *c, const uint8_t *src, size_t src_
 			return rc;
 	}
 	if (n == 0 || nsegs == 0)
-		return c ? 0 : (mi_cls_device_count() > 0 ? -EINVAL : -ENODEV);
+		return c ? 0 : no_ctx();
 	if (!src || !off || !len || !desc || !dst || !seg || !st || ((uintptr_t)desc & 15u) != 0 ||
 	    ((uintptr_t)seg & 7u) != 0)
 		return -EINVAL;
 	if (src == dst ? src_bytes != dst_bytes
 		       : (src < dst ? src + src_bytes > dst : dst + dst_bytes > src))
 		return -EINVAL;
+	if (!frames_inside(off, len, n, src_bytes))
+		return -EINVAL;
 	uint64_t owned = 0;
 	for (uint32_t i = 0; i < n; ++i) {
 		const mi_cls_lso_desc_t &d = desc[i];
-		if ((size_t)off[i] + len[i] > src_bytes || d.profile >= nprof || d.nseg < 2 ||
+		if (d.profile >= nprof || d.nseg < 2 ||
 		    d.nseg > MI_CLS_LSO_MAX_SEGMENTS || d.hdr_len > MI_CLS_LSO_MAX_PAYLOAD_OFFSET ||
 		    d.hdr_len > len[i] || d.seg_payload == 0 || (uint64_t)d.first_seg + d.nseg > nsegs)
 			return -EINVAL;
@@ -1387,15 +1400,15 @@ static int lso_host_check(const mi_cls_ctx_t *c, const uint8_t *src, size_t src_
 	if (owned != nsegs)
 		return -EINVAL;
 	if (!c)
-		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
+		return no_ctx();
 	return 0;
 }
 
 // A host batch on the context's stream: in place when everything is
-// page-locked (*staged = false: nothing waited for); else through the
-// staging buffers -- sources, descriptors and the table up, the kernel, st
-// back, and of the destination only the segments of the packets that did not
-// fail (runs of adjoining segments in one copy).  The staged form has
+// page-locked (nothing waited for; no 16-B rounding condition); else through
+// the staging buffers -- sources, descriptors and the table up, the kernel,
+// st back, and of the destination only the segments of the packets that did
+// not fail (runs of adjoining segments in one copy).  The staged form has
 // completed when it returns.
 static int lso_host_launch(mi_cls_ctx_t *c, const uint8_t *src, size_t src_bytes, const uint32_t *off,
 			   const uint16_t *len, const mi_cls_lso_desc_t *desc, uint32_t n, uint8_t *dst,
@@ -1403,31 +1416,22 @@ static int lso_host_launch(mi_cls_ctx_t *c, const uint8_t *src, size_t src_bytes
 			   const mi_cls_lso_profile_t *prof, uint32_t nprof, uint8_t *st)
 {
 	HIP_OK(set_device(c->device));
-	const void *zs = dev_view(src), *zd = zs ? dev_view(dst) : nullptr;
-	const void *zo = zd ? dev_view(off) : nullptr, *zl = zo ? dev_view(len) : nullptr;
-	const void *zc = zl ? dev_view(desc) : nullptr, *zg = zc ? dev_view(seg) : nullptr;
-	const void *zt = zg ? dev_view(st) : nullptr;
-	if (zt)
-		return mi_cls_lso_segment(c, (const uint8_t *)zs, (const uint32_t *)zo, (const uint16_t *)zl,
-					  (const mi_cls_lso_desc_t *)zc, n, (uint8_t *)zd,
-					  (const mi_cls_lso_seg_t *)zg, nsegs, prof, nprof, (uint8_t *)zt, c->stream);
-	// d_pk: the sources, then (another buffer) room for the destination, on
-	// a 256-byte boundary; d_out (16 B per entry): the descriptors, then the
-	// segment table; d_len: the lengths, then st
-	const bool same = src == dst;
-	const size_t dbase = same ? 0 : (src_bytes + 255u) & ~(size_t)255u;
-	const uint32_t cnt = 2u * n + nsegs;
-	int rc = stage_bufs(c, dbase + dst_bytes + 64, cnt);
+	const uint8_t *zs = src;
+	uint8_t *zd = dst, *zt = st;
+	const uint32_t *zo = off;
+	const uint16_t *zl = len;
+	const mi_cls_lso_desc_t *zc = desc;
+	const mi_cls_lso_seg_t *zg = seg;
+	if (dev_views(zs, zd, zo, zl, zc, zg, zt))
+		return mi_cls_lso_segment(c, zs, zo, zl, zc, n, zd, zg, nsegs, prof, nprof, zt, c->stream);
+	const size_t dbase = stg_lso_dst(src == dst, src_bytes);
+	int rc = stage_up(c, src, src_bytes, dbase + dst_bytes, off, len, n, 2u * n + nsegs);
 	if (rc)
 		return rc;
 	hipStream_t s = c->stream;
-	mi_cls_lso_desc_t *d_desc = (mi_cls_lso_desc_t *)c->d_out;
-	mi_cls_lso_seg_t *d_seg = (mi_cls_lso_seg_t *)(c->d_out + n);
-	uint8_t *d_st = (uint8_t *)(c->d_len + n);
-	uint8_t *d_dst = c->d_pk + dbase;
-	HIP_OK(hipMemcpyAsync(c->d_pk, src, src_bytes, hipMemcpyHostToDevice, s));
-	HIP_OK(hipMemcpyAsync(c->d_off, off, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-	HIP_OK(hipMemcpyAsync(c->d_len, len, n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+	mi_cls_lso_desc_t *d_desc = stg_lso_desc(c);
+	mi_cls_lso_seg_t *d_seg = stg_lso_seg(c, n);
+	uint8_t *d_st = stg_lso_st(c, n), *d_dst = c->d_pk + dbase;
 	HIP_OK(hipMemcpyAsync(d_desc, desc, n * sizeof(mi_cls_lso_desc_t), hipMemcpyHostToDevice, s));
 	HIP_OK(hipMemcpyAsync(d_seg, seg, nsegs * sizeof(mi_cls_lso_seg_t), hipMemcpyHostToDevice, s));
 	rc = mi_cls_lso_segment(c, c->d_pk, c->d_off, c->d_len, d_desc, n, d_dst, d_seg, nsegs, prof, nprof,
@@ -1462,14 +1466,12 @@ extern "C" int mi_cls_lso_segment_host(mi_cls_ctx_t *c, const uint8_t *src, size
 				       const mi_cls_lso_seg_t *seg, uint32_t nsegs,
 				       const mi_cls_lso_profile_t *prof, uint32_t nprof, uint8_t *st)
 {
-	int rc = lso_host_check(c, src, src_bytes, off, len, desc, n, dst, dst_bytes, seg, nsegs, prof, nprof, st);
+	const int rc = lso_host_check(c, src, src_bytes, off, len, desc, n, dst, dst_bytes, seg, nsegs, prof, nprof, st);
 	if (rc || n == 0 || nsegs == 0)
 		return rc;
-	rc = lso_host_launch(c, src, src_bytes, off, len, desc, n, dst, dst_bytes, seg, nsegs, prof, nprof, st);
-	if (rc)
-		return rc;
-	HIP_OK(hipStreamSynchronize(c->stream));
-	return 0;
+	return host_run(c, nullptr, [&] {
+		return lso_host_launch(c, src, src_bytes, off, len, desc, n, dst, dst_bytes, seg, nsegs, prof, nprof, st);
+	});
 }
 
 extern "C" int mi_cls_lso_segment_host_submit(mi_cls_ctx_t *c, const uint8_t *src, size_t src_bytes,
@@ -1482,27 +1484,17 @@ extern "C" int mi_cls_lso_segment_host_submit(mi_cls_ctx_t *c, const uint8_t *sr
 	if (!ticket)
 		return -EINVAL;
 	*ticket = 0;
-	int rc = lso_host_check(c, src, src_bytes, off, len, desc, n, dst, dst_bytes, seg, nsegs, prof, nprof, st);
+	const int rc = lso_host_check(c, src, src_bytes, off, len, desc, n, dst, dst_bytes, seg, nsegs, prof, nprof, st);
 	if (rc || n == 0 || nsegs == 0)
 		return rc;
-	const uint64_t t = c->submitted + 1;
-	HIP_OK(set_device(c->device));
-	if (ring_slot(c, t))
-		return -EIO;
-	rc = lso_host_launch(c, src, src_bytes, off, len, desc, n, dst, dst_bytes, seg, nsegs, prof, nprof, st);
-	if (rc)
-		return rc;
-	HIP_OK(hipEventRecord(c->ev[t % 8], c->stream));
-	c->submitted = t;
-	*ticket = t;
-	return 0;
+	return host_run(c, ticket, [&] {
+		return lso_host_launch(c, src, src_bytes, off, len, desc, n, dst, dst_bytes, seg, nsegs, prof, nprof, st);
+	});
 }
 
 extern "C" int mi_cls_lso_segment_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
 {
-	if (!c)
-		return mi_cls_device_count() > 0 ? -EINVAL : -ENODEV;
-	return mi_cls_classify_host_wait(c, ticket);
+	return feature_host_wait(c, ticket);
 }
 
 // ---------------------------------------------------------------- multi-GPU
@@ -1638,9 +1630,8 @@ extern "C" int mi_cls_group_classify_host(mi_cls_group_t *g, const uint8_t *pkts
 	for (uint32_t k = 0; k < g->n; ++k)
 		if (!g->ctx[k]->loaded)
 			return -EINVAL;
-	for (uint32_t i = 0; i < n; ++i)
-		if ((size_t)off[i] + len[i] > bytes)
-			return -EINVAL;
+	if (!frames_inside(off, len, n, bytes))
+		return -EINVAL;
 	int rc = mi_cls_shard(len, n, g->n, g->begin);
 	if (rc)
 		return rc;
@@ -1733,13 +1724,11 @@ extern "C" int mi_cls_group_classify_host_submit(mi_cls_group_t *g, const uint8_
 	for (uint32_t k = 0; k < g->n; ++k)
 		if (!g->ctx[k]->loaded)
 			return -EINVAL;
-	bool inplace = dev_view(pkts) && dev_view(off) && dev_view(len) && dev_view(out);
-	for (uint32_t i = 0; i < n; ++i) {
-		if ((size_t)off[i] + len[i] > bytes)
-			return -EINVAL;
-		if ((size_t)off[i] + (((size_t)len[i] + 15u) & ~(size_t)15u) > bytes)
-			inplace = false;   // host_launch would stage this batch
-	}
+	if (!frames_inside(off, len, n, bytes))
+		return -EINVAL;
+	// (otherwise host_launch would stage this batch)
+	const bool inplace = dev_view(pkts) && dev_view(off) && dev_view(len) && dev_view(out) &&
+			     frames_padded_inside(off, len, n, bytes);
 	if (!inplace || g->n == 1)
 		return g->n == 1 ? mi_cls_classify_host_submit(g->ctx[0], pkts, bytes, off, len, n, out, ticket)
 				 : mi_cls_group_classify_host(g, pkts, bytes, off, len, n, out);

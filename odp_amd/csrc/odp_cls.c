@@ -1625,25 +1625,32 @@ int odp_amd_cls_classify_host_wait(odp_pktio_t h, uint64_t ticket)
 	return e->ctx ? mi_cls_classify_host_wait(e->ctx, ticket) : -EINVAL;
 }
 
+/* The pktio's transmit context, created by the first call on the pktio's
+ * device (its first one when it spans several).  0, or a negative errno. */
+static int tx_ctx(odp_pktio_t h, mi_cls_ctx_t **c)
+{
+	pktio_t *e = get_pktio(h);
+	int rc = 0;
+
+	if (!e)
+		return -EINVAL;
+	if (!e->tctx)
+		rc = mi_cls_ctx_create(e->ngpu > 1 ? e->gpus[0] : e->gpu, &e->tctx);
+	*c = e->tctx;
+	return rc;
+}
+
 /* pktout checksum insertion of a send burst (mi_cls_chksum_insert_host) on
- * the pktio's transmit context, created by the first call on the pktio's
- * device (its first one when it spans several); n == 0 only creates it
- * (odp_pktio_start).  Returns when the checksums are in the frames. */
+ * the pktio's transmit context; n == 0 only creates it (odp_pktio_start).
+ * Returns when the checksums are in the frames. */
 int odp_amd_cls_chksum_insert_host(odp_pktio_t h, uint8_t *pkts, size_t bytes, const uint32_t *off,
 				   const uint16_t *len, const mi_cls_tx_desc_t *desc, uint32_t n,
 				   uint64_t pktout_opt, uint8_t *done)
 {
-	pktio_t *e = get_pktio(h);
+	mi_cls_ctx_t *tctx;
+	const int rc = tx_ctx(h, &tctx);
 
-	if (!e)
-		return -EINVAL;
-	if (!e->tctx) {
-		int rc = mi_cls_ctx_create(e->ngpu > 1 ? e->gpus[0] : e->gpu, &e->tctx);
-
-		if (rc)
-			return rc;
-	}
-	return mi_cls_chksum_insert_host(e->tctx, pkts, bytes, off, len, desc, n, pktout_opt, done);
+	return rc ? rc : mi_cls_chksum_insert_host(tctx, pkts, bytes, off, len, desc, n, pktout_opt, done);
 }
 
 /* LSO segmentation of a send call (mi_cls_lso_segment_host) on the pktio's
@@ -1653,18 +1660,11 @@ int odp_amd_cls_lso_segment_host(odp_pktio_t h, uint8_t *buf, size_t bytes, cons
 				 const mi_cls_lso_seg_t *seg, uint32_t nsegs, const mi_cls_lso_profile_t *prof,
 				 uint32_t nprof, uint8_t *st)
 {
-	pktio_t *e = get_pktio(h);
+	mi_cls_ctx_t *tctx;
+	const int rc = tx_ctx(h, &tctx);
 
-	if (!e)
-		return -EINVAL;
-	if (!e->tctx) {
-		int rc = mi_cls_ctx_create(e->ngpu > 1 ? e->gpus[0] : e->gpu, &e->tctx);
-
-		if (rc)
-			return rc;
-	}
-	return mi_cls_lso_segment_host(e->tctx, buf, bytes, off, len, desc, n, buf, bytes, seg, nsegs, prof,
-				       nprof, st);
+	return rc ? rc : mi_cls_lso_segment_host(tctx, buf, bytes, off, len, desc, n, buf, bytes, seg, nsegs,
+						 prof, nprof, st);
 }
 
 /* The parse on its own (odp_packet_parse, mi_cls_parse_host) on one

@@ -76,6 +76,25 @@ typedef struct {
 	uint64_t in_errors, in_discards, octets, packets;
 } rx_cnt_t;
 
+/* The host batch of one offload caller (pktout checksum insertion, LSO,
+ * odp_packet_parse_multi), kept across its calls: the functions are
+ * gather_*, below. */
+typedef struct {
+	uint8_t *arr;           /* one allocation the caller carves its per-entry arrays from */
+	uint32_t cap;           /* entries */
+	int pinned;
+	uint8_t *stage;         /* bounce buffer */
+	size_t stage_cap;
+	int stage_pinned;
+	uint64_t bursts, bounced;   /* calls that ran the kernel / of them through the bounce buffer */
+	/* the call in hand */
+	int in_place;
+	uint8_t *lo;            /* the page-locked arena */
+	size_t span;
+	uint8_t *base;          /* what the GPU entry is given: the arena or the bounce buffer, */
+	size_t bytes, pos;      /* its size; the next bounce offset */
+} gather_t;
+
 /* One receive burst on its way through the GPU. */
 typedef struct {
 	uint8_t *stage;         /* copies of the frames (64 B aligned offsets) */
@@ -177,35 +196,10 @@ typedef struct {
 	uint64_t rxtab_gen;
 	odp_pool_t rx_pools[MI_CLS_RX_POOLS];
 	uint32_t rx_np, rx_want[MI_CLS_RX_POOLS];
-	/* transmit (pktout checksum insertion): a send burst's descriptors in
-	 * page-locked memory, and the bounce buffer of bursts with a packet
-	 * outside the page-locked arena (pageable pools) */
+	/* transmit: the gathers of pktout checksum insertion (a send burst) and
+	 * of LSO (an odp_pktout_send_lso call), both under txl */
 	pthread_mutex_t txl;    /* held across the kernel's launch and wait */
-	uint8_t *tx_arr;        /* one allocation: tx_desc, tx_off, tx_len (tx_cap each) */
-	mi_cls_tx_desc_t *tx_desc;
-	uint32_t *tx_off;
-	uint16_t *tx_len;
-	uint32_t tx_cap;
-	int tx_pinned;
-	uint64_t tx_bursts, tx_bounced;   /* send calls that ran the kernel / of them
-					   * through the bounce buffer */
-	uint8_t *tx_stage;
-	size_t tx_stage_cap;
-	int tx_stage_pinned;
-	/* LSO (odp_pktout_send_lso): a call's descriptors, segment table and
-	 * status bytes in page-locked memory, and its bounce buffer; under txl */
-	uint8_t *lso_arr;       /* one allocation: lso_desc, lso_seg, lso_off, lso_len, lso_st */
-	mi_cls_lso_desc_t *lso_desc;
-	mi_cls_lso_seg_t *lso_seg;
-	uint32_t *lso_off;
-	uint16_t *lso_len;
-	uint8_t *lso_st;
-	uint32_t lso_cap;       /* sources; 64 segments each */
-	int lso_pinned;
-	uint8_t *lso_stage;
-	size_t lso_stage_cap;
-	int lso_stage_pinned;
-	uint64_t lso_bursts, lso_bounced;   /* as tx_bursts / tx_bounced */
+	gather_t txg, lsog;
 	uint64_t prof[16];      /* ODP_AMD_RX_PROF: ns staging / classifying / delivering, bursts,
 				 * then of delivering: ns preparing / enqueueing, TSC ticks in
 				 * packet allocation / frame copies; GPU delivery: ns deciding +
@@ -3188,24 +3182,118 @@ int odp_pktin_recv_tmo(odp_pktin_queue_t q, odp_packet_t pkts[], int num, uint64
 }
 
 /* ============================================================ transmit */
+/* The gather of an offload call (gather_t), stated once for its three
+ * callers.  A call's descriptors are built in page-locked arrays carved out
+ * of one allocation.  Its frames are worked on in place where every piece
+ * lies in the page-locked arena (rt_pinned_arena; below OOB_SPAN, so that
+ * arena-relative offsets stay under the kernels' out-of-range offset), in a
+ * page-locked pool, with `slack` readable bytes behind it; a call with one
+ * piece elsewhere (pageable pools) goes whole through a page-locked bounce
+ * buffer, its pieces at 64-B steps.
+ *   minimum capacity:  checksum 4096 packets, parse 1024, LSO 64 sources
+ *   slack:             checksum and parse 16 B (their kernels read frames in
+ *                      16-B pieces), LSO sources and segments 0
+ *   length clamp:      checksum and parse 65535 (GATHER_LEN_MAX); LSO plans
+ *                      no longer packet
+ *   refused:           a bounce layout of OOB_SPAN or more (-E2BIG), no
+ *                      memory (-ENOMEM); checksum and parse report both as
+ *                      their plain failure
+ *   copied back:       checksum every frame, parse nothing, LSO the segments
+ *                      of the packets with st == OK
+ * Everything here runs under the caller's lock (txl, PRS.lock). */
+#define GATHER_LEN_MAX 65535u
+
+/* Begin a call of n entries, `per` bytes of arrays each: g->arr holds g->cap
+ * (>= n, >= min_cap) entries of every array.  0, or -ENOMEM. */
+static int gather_begin(gather_t *g, uint32_t n, size_t per, uint32_t min_cap)
+{
+	if (n > g->cap) {
+		const size_t cap = n < min_cap ? min_cap : (size_t)n + n / 2;
+
+		hmem_free(g->arr, g->pinned);
+		g->cap = 0;
+		g->arr = hmem_alloc(cap * per, &g->pinned);
+		if (!g->arr)
+			return -ENOMEM;
+		g->cap = (uint32_t)cap;
+	}
+	g->lo = NULL;
+	g->span = g->bytes = 0;
+	g->in_place = g->pinned && rt_pinned_arena(&g->lo, &g->span) && g->span < OOB_SPAN;
+	return 0;
+}
+
+static inline int pkt_pool_pinned(const pkt_hdr_t *h)
+{
+	const rt_pool_t *rp = rt_pool((odp_pool_t)(uintptr_t)(h->ev.pool + 1u));
+
+	return rp && rp->pinned;
+}
+
+/* Place a piece: its arena-relative offset, or the call drops to the bounce
+ * path (and gather_step gives the offset). */
+static inline uint32_t gather_place(gather_t *g, const uint8_t *d, uint32_t len, uint32_t slack, int pool_pinned)
+{
+	g->bytes += (len + 63u) & ~63u;
+	if (g->in_place && pool_pinned && d >= g->lo && (size_t)(d - g->lo) + len + slack <= g->span)
+		return (uint32_t)(d - g->lo);
+	g->in_place = 0;
+	return 0;
+}
+
+/* After the last piece, g->base / g->bytes for the GPU entry: 0 in place; 1
+ * through the bounce buffer, reserved here, where the caller now lays its
+ * pieces out in the order it placed them (gather_step); or < 0. */
+static int gather_layout(gather_t *g)
+{
+	if (g->in_place) {
+		g->base = g->lo;
+		g->bytes = g->span;
+		return 0;
+	}
+	g->bytes += 64;
+	if (g->bytes >= OOB_SPAN)
+		return -E2BIG;
+	if (g->bytes > g->stage_cap) {
+		hmem_free(g->stage, g->stage_pinned);
+		g->stage_cap = 0;
+		g->stage = hmem_alloc(g->bytes + g->bytes / 2, &g->stage_pinned);
+		if (!g->stage)
+			return -ENOMEM;
+		g->stage_cap = g->bytes + g->bytes / 2;
+	}
+	g->base = g->stage;
+	g->pos = 0;
+	return 1;
+}
+
+static inline uint32_t gather_step(gather_t *g, uint32_t len)
+{
+	const size_t off = g->pos;
+
+	g->pos += (len + 63u) & ~63u;
+	return (uint32_t)off;
+}
+
+/* The call's kernel ran */
+static inline void gather_ran(gather_t *g)
+{
+	g->bursts++;
+	g->bounced += !g->in_place;
+}
+
+static void gather_free(gather_t *g)
+{
+	hmem_free(g->arr, g->pinned);
+	hmem_free(g->stage, g->stage_pinned);
+	memset(g, 0, sizeof(*g));
+}
+
 static void tx_free(rt_pktio_t *e)
 {
-	hmem_free(e->tx_arr, e->tx_pinned);
-	hmem_free(e->tx_stage, e->tx_stage_pinned);
-	hmem_free(e->lso_arr, e->lso_pinned);
-	hmem_free(e->lso_stage, e->lso_stage_pinned);
-	e->lso_arr = NULL;
-	e->lso_stage = NULL;
-	e->lso_cap = 0;
-	e->lso_stage_cap = 0;
+	gather_free(&e->txg);
+	gather_free(&e->lsog);
 	pthread_mutex_destroy(&e->txl);
-	e->tx_arr = NULL;
-	e->tx_off = NULL;
-	e->tx_len = NULL;
-	e->tx_desc = NULL;
-	e->tx_stage = NULL;
-	e->tx_cap = 0;
-	e->tx_stage_cap = 0;
 }
 
 /* pktout checksum insertion of a send burst on a loop pktio
@@ -3236,79 +3324,44 @@ static int tx_chksum(rt_pktio_t *e, const odp_packet_t pkts[], int num)
 	const uint32_t n = (uint32_t)num;
 	int rc = -1;
 
-	pthread_mutex_lock(&e->txl);
-	if (n > e->tx_cap) {
-		const size_t cap = n < 4096u ? 4096u : (size_t)n + n / 2;
+	gather_t *g = &e->txg;
 
-		hmem_free(e->tx_arr, e->tx_pinned);
-		e->tx_cap = 0;
-		e->tx_arr = hmem_alloc(cap * (sizeof(mi_cls_tx_desc_t) + sizeof(uint32_t) + sizeof(uint16_t)),
-				       &e->tx_pinned);
-		if (!e->tx_arr)
-			goto out;
-		e->tx_desc = (mi_cls_tx_desc_t *)(void *)e->tx_arr;
-		e->tx_off = (uint32_t *)(void *)(e->tx_desc + cap);
-		e->tx_len = (uint16_t *)(void *)(e->tx_off + cap);
-		e->tx_cap = (uint32_t)cap;
-	}
-	uint8_t *lo = NULL, *base;
-	size_t span = 0, bytes = 0;
-	int in_place = e->tx_pinned && rt_pinned_arena(&lo, &span) && span < OOB_SPAN;
+	pthread_mutex_lock(&e->txl);
+	if (gather_begin(g, n, sizeof(mi_cls_tx_desc_t) + sizeof(uint32_t) + sizeof(uint16_t), 4096))
+		goto out;
+	mi_cls_tx_desc_t *desc = (mi_cls_tx_desc_t *)(void *)g->arr;
+	uint32_t *off = (uint32_t *)(void *)(desc + g->cap);
+	uint16_t *len = (uint16_t *)(void *)(off + g->cap);
 
 	for (uint32_t i = 0; i < n; i++) {
 		const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
-		const uint8_t *d = h->head + h->data_off;
-		const uint32_t l = h->len > 65535 ? 65535 : h->len;
-		const rt_pool_t *rp = rt_pool((odp_pool_t)(uintptr_t)(h->ev.pool + 1u));
 
-		e->tx_len[i] = (uint16_t)l;
-		e->tx_desc[i] = (mi_cls_tx_desc_t){ .l3 = h->l3, .l4 = h->l4, .flags = (uint8_t)(h->tx_ck & 0xFu) };
-		if (in_place && rp && rp->pinned && d >= lo && (size_t)(d - lo) + l + 16u <= span)
-			e->tx_off[i] = (uint32_t)(d - lo);
-		else
-			in_place = 0;
-		bytes += (l + 63u) & ~63u;
+		len[i] = (uint16_t)(h->len > GATHER_LEN_MAX ? GATHER_LEN_MAX : h->len);
+		desc[i] = (mi_cls_tx_desc_t){ .l3 = h->l3, .l4 = h->l4, .flags = (uint8_t)(h->tx_ck & 0xFu) };
+		off[i] = gather_place(g, h->head + h->data_off, len[i], 16, pkt_pool_pinned(h));
 	}
-	if (in_place) {
-		base = lo;
-		bytes = span;
-	} else {
-		bytes += 64;
-		if (bytes >= OOB_SPAN)
-			goto out;
-		if (bytes > e->tx_stage_cap) {
-			hmem_free(e->tx_stage, e->tx_stage_pinned);
-			e->tx_stage_cap = 0;
-			e->tx_stage = hmem_alloc(bytes + bytes / 2, &e->tx_stage_pinned);
-			if (!e->tx_stage)
-				goto out;
-			e->tx_stage_cap = bytes + bytes / 2;
-		}
-		size_t off = 0;
+	const int bounce = gather_layout(g);
 
-		for (uint32_t i = 0; i < n; i++) {
-			const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
+	if (bounce < 0)
+		goto out;
+	for (uint32_t i = 0; bounce && i < n; i++) {
+		const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
 
-			memcpy(e->tx_stage + off, h->head + h->data_off, e->tx_len[i]);
-			e->tx_off[i] = (uint32_t)off;
-			off += (e->tx_len[i] + 63u) & ~63u;
-		}
-		base = e->tx_stage;
+		off[i] = gather_step(g, len[i]);
+		memcpy(g->stage + off[i], h->head + h->data_off, len[i]);
 	}
-	rc = odp_amd_cls_chksum_insert_host(e->hdl, base, bytes, e->tx_off, e->tx_len, e->tx_desc, n, opt,
-					    NULL);
+	rc = odp_amd_cls_chksum_insert_host(e->hdl, g->base, g->bytes, off, len, desc, n, opt, NULL);
 	if (rc) {
 		RT_ERR("pktio %s: pktout checksum insertion failed (%s)\n", e->name, mi_cls_strerror(rc));
 		rc = -1;
 		goto out;
 	}
-	for (uint32_t i = 0; !in_place && i < n; i++) {
+	for (uint32_t i = 0; bounce && i < n; i++) {
 		pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
 
-		memcpy(h->head + h->data_off, e->tx_stage + e->tx_off[i], e->tx_len[i]);
+		memcpy(h->head + h->data_off, g->stage + off[i], len[i]);
 	}
-	e->tx_bursts++;
-	e->tx_bounced += !in_place;
+	gather_ran(g);
 out:
 	pthread_mutex_unlock(&e->txl);
 	return rc;
@@ -3320,17 +3373,8 @@ out:
  * time; page-locked where there is a GPU; kept for the process's life. */
 static struct {
 	pthread_mutex_t lock;
-	uint8_t *arr;
-	mi_cls_result_t *res;   /* arr: records, offsets, lengths */
-	uint32_t *off;
-	uint16_t *len;
-	uint32_t cap;
-	int pinned;
-	uint8_t *stage;
-	size_t stage_cap;
-	int stage_pinned;
+	gather_t g;             /* arrays: records, offsets, lengths */
 	int no_gpu_said;
-	uint64_t calls, bounced;   /* kernel launches / of them through the bounce buffer */
 } PRS = { .lock = PTHREAD_MUTEX_INITIALIZER };
 
 /* odp_packet_parse_multi (odp_packet.c:2219-2229 over odp_packet_parse,
@@ -3360,69 +3404,34 @@ int odp_packet_parse_multi(const odp_packet_t pkts[], const uint32_t offset[], i
 		return 0;
 	int done = 0;
 
-	pthread_mutex_lock(&PRS.lock);
-	if (n > PRS.cap) {
-		const size_t cap = n < 1024u ? 1024u : (size_t)n + n / 2;
+	gather_t *g = &PRS.g;
 
-		hmem_free(PRS.arr, PRS.pinned);
-		PRS.cap = 0;
-		PRS.arr = hmem_alloc(cap * (sizeof(mi_cls_result_t) + sizeof(uint32_t) + sizeof(uint16_t)),
-				     &PRS.pinned);
-		if (!PRS.arr)
-			goto out;
-		PRS.res = (mi_cls_result_t *)(void *)PRS.arr;
-		PRS.off = (uint32_t *)(void *)(PRS.res + cap);
-		PRS.len = (uint16_t *)(void *)(PRS.off + cap);
-		PRS.cap = (uint32_t)cap;
-	}
-	uint8_t *lo = NULL;
-	const uint8_t *base;
-	size_t span = 0, bytes = 0;
-	int in_place = PRS.pinned && rt_pinned_arena(&lo, &span) && span < OOB_SPAN;
+	pthread_mutex_lock(&PRS.lock);
+	if (gather_begin(g, n, sizeof(mi_cls_result_t) + sizeof(uint32_t) + sizeof(uint16_t), 1024))
+		goto out;
+	mi_cls_result_t *res = (mi_cls_result_t *)(void *)g->arr;
+	uint32_t *off = (uint32_t *)(void *)(res + g->cap);
+	uint16_t *len = (uint16_t *)(void *)(off + g->cap);
 
 	for (uint32_t i = 0; i < n; i++) {
 		const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
-		const uint8_t *d = h->head + h->data_off + offset[i];
 		const uint32_t rest = h->len - offset[i];
-		const uint32_t l = rest > 65535 ? 65535 : rest;
-		const rt_pool_t *rp = rt_pool((odp_pool_t)(uintptr_t)(h->ev.pool + 1u));
 
-		PRS.len[i] = (uint16_t)l;
-		if (in_place && rp && rp->pinned && d >= lo && (size_t)(d - lo) + l + 16u <= span)
-			PRS.off[i] = (uint32_t)(d - lo);
-		else
-			in_place = 0;
-		bytes += (l + 63u) & ~63u;
+		len[i] = (uint16_t)(rest > GATHER_LEN_MAX ? GATHER_LEN_MAX : rest);
+		off[i] = gather_place(g, h->head + h->data_off + offset[i], len[i], 16, pkt_pool_pinned(h));
 	}
-	if (in_place) {
-		base = lo;
-		bytes = span;
-	} else {
-		bytes += 64;
-		if (bytes >= OOB_SPAN)
-			goto out;
-		if (bytes > PRS.stage_cap) {
-			hmem_free(PRS.stage, PRS.stage_pinned);
-			PRS.stage_cap = 0;
-			PRS.stage = hmem_alloc(bytes + bytes / 2, &PRS.stage_pinned);
-			if (!PRS.stage)
-				goto out;
-			PRS.stage_cap = bytes + bytes / 2;
-		}
-		size_t off = 0;
+	const int bounce = gather_layout(g);
 
-		for (uint32_t i = 0; i < n; i++) {
-			const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
+	if (bounce < 0)
+		goto out;
+	for (uint32_t i = 0; bounce && i < n; i++) {
+		const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
 
-			memcpy(PRS.stage + off, h->head + h->data_off + offset[i], PRS.len[i]);
-			PRS.off[i] = (uint32_t)off;
-			off += (PRS.len[i] + 63u) & ~63u;
-		}
-		base = PRS.stage;
+		off[i] = gather_step(g, len[i]);
+		memcpy(g->stage + off[i], h->head + h->data_off + offset[i], len[i]);
 	}
-	const int rc = odp_amd_cls_parse_host(base, bytes, PRS.off, PRS.len, n, (uint32_t)param->proto,
-					      (uint32_t)param->last_layer, param->chksums.all_chksum & 0xFu,
-					      PRS.res);
+	const int rc = odp_amd_cls_parse_host(g->base, g->bytes, off, len, n, (uint32_t)param->proto,
+					      (uint32_t)param->last_layer, param->chksums.all_chksum & 0xFu, res);
 
 	if (rc) {
 		/* no CPU parser stands in (as odp_pktio_start without a GPU) */
@@ -3431,11 +3440,10 @@ int odp_packet_parse_multi(const odp_packet_t pkts[], const uint32_t offset[], i
 		PRS.no_gpu_said |= rc == -ENODEV;
 		goto out;
 	}
-	PRS.calls++;
-	PRS.bounced += !in_place;
+	gather_ran(g);
 	for (uint32_t i = 0; i < n; i++) {
 		pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
-		const mi_cls_result_t *r = &PRS.res[i];
+		const mi_cls_result_t *r = &res[i];
 		const uint32_t o = offset[i];
 
 		/* packet_parse_reset(hdr, 0): the input flags and error bits are
@@ -3462,8 +3470,8 @@ int odp_packet_parse(odp_packet_t pkt, uint32_t offset, const odp_packet_parse_p
 void odp_amd_packet_parse_stats(uint64_t *calls, uint64_t *bounced)
 {
 	pthread_mutex_lock(&PRS.lock);
-	*calls = PRS.calls;
-	*bounced = PRS.bounced;
+	*calls = PRS.g.bursts;
+	*bounced = PRS.g.bounced;
 	pthread_mutex_unlock(&PRS.lock);
 }
 
@@ -3695,110 +3703,70 @@ static int lso_launch(rt_pktio_t *e, const odp_packet_t pkts[], lso_plan_t *pl, 
 	int rc = -ENOMEM;
 
 	lso_table(tab);
-	pthread_mutex_lock(&e->txl);
-	if (nsrc > e->lso_cap) {
-		const size_t cap = nsrc < 64u ? 64u : (size_t)nsrc + nsrc / 2;
+	gather_t *g = &e->lsog;
 
-		hmem_free(e->lso_arr, e->lso_pinned);
-		e->lso_cap = 0;
-		e->lso_arr = hmem_alloc(cap * (sizeof(mi_cls_lso_desc_t) + MI_CLS_LSO_MAX_SEGMENTS * sizeof(mi_cls_lso_seg_t) +
-					       sizeof(uint32_t) + sizeof(uint16_t) + 1u), &e->lso_pinned);
-		if (!e->lso_arr)
-			goto out;
-		e->lso_desc = (mi_cls_lso_desc_t *)(void *)e->lso_arr;
-		e->lso_seg = (mi_cls_lso_seg_t *)(void *)(e->lso_desc + cap);
-		e->lso_off = (uint32_t *)(void *)(e->lso_seg + cap * MI_CLS_LSO_MAX_SEGMENTS);
-		e->lso_len = (uint16_t *)(void *)(e->lso_off + cap);
-		e->lso_st = (uint8_t *)(void *)(e->lso_len + cap);
-		e->lso_cap = (uint32_t)cap;
-	}
-	uint8_t *lo = NULL, *base;
-	size_t span = 0, bytes = 0;
-	int in_place = e->lso_pinned && rt_pinned_arena(&lo, &span) && span < OOB_SPAN;
+	pthread_mutex_lock(&e->txl);
+	if (gather_begin(g, nsrc, sizeof(mi_cls_lso_desc_t) + MI_CLS_LSO_MAX_SEGMENTS * sizeof(mi_cls_lso_seg_t) +
+			 sizeof(uint32_t) + sizeof(uint16_t) + 1u, 64))
+		goto out;
+	/* per source: descriptor, MI_CLS_LSO_MAX_SEGMENTS segment entries, offset, length, status */
+	mi_cls_lso_desc_t *desc = (mi_cls_lso_desc_t *)(void *)g->arr;
+	mi_cls_lso_seg_t *seg = (mi_cls_lso_seg_t *)(void *)(desc + g->cap);
+	uint32_t *off = (uint32_t *)(void *)(seg + (size_t)g->cap * MI_CLS_LSO_MAX_SEGMENTS);
+	uint16_t *len = (uint16_t *)(void *)(off + g->cap);
+	uint8_t *st = (uint8_t *)(void *)(len + g->cap);
 	uint32_t k = 0;
 
 	for (int i = 0; i < end; i++) {
 		if (pl[i].nseg < 2)
 			continue;
 		const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
-		const uint8_t *d = h->head + h->data_off;
-		const rt_pool_t *rp = rt_pool((odp_pool_t)(uintptr_t)(h->ev.pool + 1u));
 
-		e->lso_len[k] = (uint16_t)h->len;
-		e->lso_desc[k] = (mi_cls_lso_desc_t){ .hdr_len = (uint16_t)pl[i].hdr, .seg_payload = (uint16_t)pl[i].pay,
-						      .l3 = (uint16_t)pl[i].l3, .profile = pl[i].prof,
-						      .nseg = (uint8_t)pl[i].nseg, .first_seg = pl[i].first };
-		e->lso_st[k] = 0;
-		/* the segments come from the source's pool: one test serves both */
-		if (in_place && rp && rp->pinned && d >= lo && (size_t)(d - lo) + h->len <= span)
-			e->lso_off[k] = (uint32_t)(d - lo);
-		else
-			in_place = 0;
-		bytes += (h->len + 63u) & ~63u;
-		for (int s = 0; s < pl[i].nseg; s++) {
-			const pkt_hdr_t *sh = rt_pkt_hdr(segs[pl[i].first + (uint32_t)s]);
-			const uint8_t *sd = sh->head + sh->data_off;
+		len[k] = (uint16_t)h->len;
+		desc[k] = (mi_cls_lso_desc_t){ .hdr_len = (uint16_t)pl[i].hdr, .seg_payload = (uint16_t)pl[i].pay,
+					       .l3 = (uint16_t)pl[i].l3, .profile = pl[i].prof,
+					       .nseg = (uint8_t)pl[i].nseg, .first_seg = pl[i].first };
+		st[k] = 0;
+		off[k] = gather_place(g, h->head + h->data_off, h->len, 0, pkt_pool_pinned(h));
+		/* the segments come from the source's pool: its test serves them */
+		for (uint32_t j = pl[i].first; j < pl[i].first + (uint32_t)pl[i].nseg; j++) {
+			const pkt_hdr_t *sh = rt_pkt_hdr(segs[j]);
 
-			e->lso_seg[pl[i].first + (uint32_t)s].src = k;
-			if (in_place && sd >= lo && (size_t)(sd - lo) + sh->len <= span)
-				e->lso_seg[pl[i].first + (uint32_t)s].off = (uint32_t)(sd - lo);
-			else
-				in_place = 0;
-			bytes += (sh->len + 63u) & ~63u;
+			seg[j].src = k;
+			seg[j].off = gather_place(g, sh->head + sh->data_off, sh->len, 0, 1);
 		}
 		k++;
 	}
-	if (in_place) {
-		base = lo;
-		bytes = span;
-	} else {
-		bytes += 64;
-		rc = -E2BIG;
-		if (bytes >= OOB_SPAN)
-			goto out;
-		rc = -ENOMEM;
-		if (bytes > e->lso_stage_cap) {
-			hmem_free(e->lso_stage, e->lso_stage_pinned);
-			e->lso_stage_cap = 0;
-			e->lso_stage = hmem_alloc(bytes + bytes / 2, &e->lso_stage_pinned);
-			if (!e->lso_stage)
-				goto out;
-			e->lso_stage_cap = bytes + bytes / 2;
-		}
-		size_t off = 0;
+	const int bounce = rc = gather_layout(g);
 
-		k = 0;
-		for (int i = 0; i < end; i++) {
-			if (pl[i].nseg < 2)
-				continue;
-			const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
+	if (bounce < 0)
+		goto out;
+	k = 0;
+	for (int i = 0; bounce && i < end; i++) {
+		if (pl[i].nseg < 2)
+			continue;
+		const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
 
-			memcpy(e->lso_stage + off, h->head + h->data_off, h->len);
-			e->lso_off[k++] = (uint32_t)off;
-			off += (h->len + 63u) & ~63u;
-			for (int s = 0; s < pl[i].nseg; s++) {
-				e->lso_seg[pl[i].first + (uint32_t)s].off = (uint32_t)off;
-				off += (rt_pkt_hdr(segs[pl[i].first + (uint32_t)s])->len + 63u) & ~63u;
-			}
-		}
-		base = e->lso_stage;
+		off[k] = gather_step(g, h->len);
+		memcpy(g->stage + off[k++], h->head + h->data_off, h->len);
+		for (uint32_t j = pl[i].first; j < pl[i].first + (uint32_t)pl[i].nseg; j++)
+			seg[j].off = gather_step(g, rt_pkt_hdr(segs[j])->len);
 	}
-	rc = odp_amd_cls_lso_segment_host(e->hdl, base, bytes, e->lso_off, e->lso_len, e->lso_desc, nsrc, e->lso_seg,
-					  nsegs, tab, MI_CLS_LSO_PROFILES, e->lso_st);
+	rc = odp_amd_cls_lso_segment_host(e->hdl, g->base, g->bytes, off, len, desc, nsrc, seg, nsegs, tab,
+					  MI_CLS_LSO_PROFILES, st);
 	if (rc)
 		goto out;
-	for (uint32_t j = 0; !in_place && j < nsegs; j++) {
+	for (uint32_t j = 0; bounce && j < nsegs; j++) {
 		pkt_hdr_t *sh = rt_pkt_hdr(segs[j]);
 
-		if (e->lso_st[e->lso_seg[j].src] == MI_CLS_LSO_ST_OK)
-			memcpy(sh->head + sh->data_off, e->lso_stage + e->lso_seg[j].off, sh->len);
+		if (st[seg[j].src] == MI_CLS_LSO_ST_OK)
+			memcpy(sh->head + sh->data_off, g->stage + seg[j].off, sh->len);
 	}
 	k = 0;
 	for (int i = 0; i < end; i++)
 		if (pl[i].nseg >= 2)
-			pl[i].st = e->lso_st[k++];
-	e->lso_bursts++;
-	e->lso_bounced += !in_place;
+			pl[i].st = st[k++];
+	gather_ran(g);
 out:
 	pthread_mutex_unlock(&e->txl);
 	return rc;
@@ -3972,8 +3940,8 @@ int odp_amd_pktio_lso_stats(odp_pktio_t h, uint64_t *bursts, uint64_t *bounced)
 	if (!e || !bursts || !bounced)
 		return -1;
 	pthread_mutex_lock(&e->txl);
-	*bursts = e->lso_bursts;
-	*bounced = e->lso_bounced;
+	*bursts = e->lsog.bursts;
+	*bounced = e->lsog.bounced;
 	pthread_mutex_unlock(&e->txl);
 	return 0;
 }
@@ -4096,8 +4064,8 @@ int odp_amd_pktio_tx_stats(odp_pktio_t h, uint64_t *bursts, uint64_t *bounced)
 	if (!e || !bursts || !bounced)
 		return -1;
 	pthread_mutex_lock(&e->txl);
-	*bursts = e->tx_bursts;
-	*bounced = e->tx_bounced;
+	*bursts = e->txg.bursts;
+	*bounced = e->txg.bounced;
 	pthread_mutex_unlock(&e->txl);
 	return 0;
 }

@@ -33,6 +33,17 @@
  *           threads parsing ten packets each at the same time, "T <thread>
  *           <i> <return> <flags> <err> <l2> <l3> <l4>"; and "B <1 if any call
  *           went through the bounce buffer>".
+ *
+ *        parse_driver batch <file>
+ *     Whole odp_packet_parse_multi calls of any size, over one or two pools
+ *     ("parse_pool", "parse_pool2": ODP_AMD_PAGEABLE_POOLS picks which are
+ *     pageable).  <file> lines:
+ *       F <hex frame>       one more frame of the frame list
+ *       B <n> <pools>       one call (ETH, ALL, all checksums) on n packets:
+ *           packet i holds frame i % frames behind L2 offset i % 10 and comes
+ *           from pool i % pools.  Output: "Q <return> <calls> <bounced>" (what
+ *           odp_amd_packet_parse_stats counted for this call) and per packet
+ *           "QP <i> <flags> <err> <l2> <l3> <l4>".
  */
 #define _GNU_SOURCE
 #include <inttypes.h>
@@ -288,21 +299,74 @@ static void two_threads(const uint8_t *frame, uint32_t len)
 	}
 }
 
+#define BATCH_FRAMES 32
+#define BATCH_MAX 2048
+
+static int batch(FILE *f, odp_pool_t pool2)
+{
+	static char line[8192], hex[4096];
+	static uint8_t frame[BATCH_FRAMES][2048];
+	static odp_packet_t pkt[BATCH_MAX];
+	static uint32_t offs[BATCH_MAX];
+	uint32_t flen[BATCH_FRAMES];
+	const odp_pool_t pools[2] = { pool, pool2 };
+	const odp_packet_parse_param_t parse = { ODP_PROTO_ETH, ODP_PROTO_LAYER_ALL, { .all_chksum = 0xF } };
+	unsigned nf = 0, n, np;
+
+	while (fgets(line, sizeof(line), f)) {
+		if (sscanf(line, "F %4095s", hex) == 1) {
+			const int l = nf < BATCH_FRAMES ? unhex(hex, frame[nf], sizeof(frame[nf])) : -1;
+
+			if (l <= 0)
+				return 5;
+			flen[nf++] = (uint32_t)l;
+		} else if (sscanf(line, "B %u %u", &n, &np) == 2) {
+			uint64_t c0, b0, c1, b1;
+
+			if (!nf || !n || n > BATCH_MAX || np < 1 || np > 2)
+				return 5;
+			for (unsigned i = 0; i < n; i++) {
+				pool = pools[i % np];
+				offs[i] = l2_offset[i % NPKT];
+				pkt[i] = mkpkt(frame[i % nf], flen[i % nf], offs[i]);
+			}
+			pool = pools[0];
+			odp_amd_packet_parse_stats(&c0, &b0);
+			const int r = odp_packet_parse_multi(pkt, offs, (int)n, &parse);
+
+			odp_amd_packet_parse_stats(&c1, &b1);
+			printf("Q %d %" PRIu64 " %" PRIu64 "\n", r, c1 - c0, b1 - b0);
+			for (unsigned i = 0; i < n; i++) {
+				char tag[32];
+
+				snprintf(tag, sizeof(tag), "QP %u", i);
+				meta_line(tag, pkt[i]);
+				printf("\n");
+			}
+			odp_packet_free_multi(pkt, (int)n);
+		}
+	}
+	return 0;
+}
+
 int main(int argc, char *argv[])
 {
 	odp_pool_param_t pp;
 
-	if (argc < 2 || (strcmp(argv[1], "surface") && (strcmp(argv[1], "run") || argc < 3))) {
-		fprintf(stderr, "usage: %s surface | run <file>\n", argv[0]);
+	if (argc < 2 || (strcmp(argv[1], "surface") &&
+			 ((strcmp(argv[1], "run") && strcmp(argv[1], "batch")) || argc < 3))) {
+		fprintf(stderr, "usage: %s surface | run <file> | batch <file>\n", argv[0]);
 		return 2;
 	}
+	const int is_batch = strcmp(argv[1], "batch") == 0;
+
 	if (odp_init_global(&inst, NULL, NULL) || odp_init_local(inst, ODP_THREAD_CONTROL))
 		return 3;
 	odp_pool_param_init(&pp);
 	pp.type = ODP_POOL_PACKET;
 	pp.pkt.len = 1856;
 	pp.pkt.seg_len = 1856;
-	pp.pkt.num = 256;
+	pp.pkt.num = is_batch ? BATCH_MAX : 256;
 	pool = odp_pool_create("parse_pool", &pp);
 	if (pool == ODP_POOL_INVALID)
 		return 3;
@@ -315,6 +379,18 @@ int main(int argc, char *argv[])
 
 	if (!f)
 		return 4;
+	if (is_batch) {
+		odp_pool_t pool2 = odp_pool_create("parse_pool2", &pp);
+		const int rc = pool2 == ODP_POOL_INVALID ? 3 : batch(f, pool2);
+
+		fclose(f);
+		if (rc)
+			return rc;
+		odp_pool_destroy(pool2);
+		odp_pool_destroy(pool);
+		odp_term_local();
+		return odp_term_global(inst) ? 6 : 0;
+	}
 	while (fgets(line, sizeof(line), f)) {
 		int proto, layer;
 		unsigned sel, plus;

@@ -359,3 +359,66 @@ def test_runtime_pageable_pool(driver, tmp_path):
     strip = lambda L: [p for p in L if p[0] != "B"]  # noqa: E731
     assert strip(paged) == strip(lines)
     assert ["B", "0"] in lines and ["B", "1"] in paged   # in place / bounced
+
+
+# ---- whole calls of any size over one or two pools (parse_driver batch): the
+# gather of odp_packet_parse_multi -- arrays that grow, a call that mixes a
+# page-locked and a pageable pool
+def _run_batch(tmp_path, calls, env_extra=None):
+    """calls: [(packets, pools)].  Returns the golden frames and, per call,
+    ((return, calls counted, bounced), [(flags, err, l2, l3, l4)])."""
+    d, _ = _cases()
+    frames = [bytes.fromhex(v["frame"]) for _, v in sorted(d.items())]
+    script = tmp_path / "batch.txt"
+    with open(script, "w") as f:
+        for fr in frames:
+            f.write(f"F {fr.hex()}\n")
+        for n, pools in calls:
+            f.write(f"B {n} {pools}\n")
+    env = dict(os.environ)
+    env.update(env_extra or {})
+    r = subprocess.run([PARSE_DRIVER, "batch", str(script)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=120, env=env)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    out = []
+    for p in (ln.split() for ln in r.stdout.splitlines()):
+        if p[0] == "Q":
+            out.append((tuple(int(x) for x in p[1:]), []))
+        elif p[0] == "QP":
+            assert int(p[1]) == len(out[-1][1])
+            out[-1][1].append(tuple(int(x, 0) for x in p[2:]))
+    assert [len(pk) for _, pk in out] == [n for n, _ in calls]
+    return frames, out
+
+
+def _batch_model(frames, n):
+    memo = {}
+    for i in range(n):
+        key = (i % len(frames), i % len(PM.REF_OFFSETS))
+        if key not in memo:
+            o = PM.REF_OFFSETS[key[1]]
+            ret, *meta = PM.parse(PM.shifted(frames[key[0]], o), o, PM.PROTO_ETH, PM.ALL, 0xF)
+            assert ret == 0
+            memo[key] = tuple(meta)
+    return [memo[(i % len(frames), i % len(PM.REF_OFFSETS))] for i in range(n)]
+
+
+def test_runtime_burst_mixing_pools(built, gpu, tmp_path):
+    """One call over 16 packets that alternate between a page-locked and a
+    pageable pool: the output of the same frames from one page-locked pool;
+    one call counted, and it bounced."""
+    frames, one = _run_batch(tmp_path, [(16, 1)])
+    _, mixed = _run_batch(tmp_path, [(16, 2)], {"ODP_AMD_PAGEABLE_POOLS": "parse_pool2"})
+    assert one[0][0] == (16, 1, 0) and mixed[0][0] == (16, 1, 1)
+    assert mixed[0][1] == one[0][1] == _batch_model(frames, 16)
+
+
+@pytest.mark.parametrize("pageable", [False, True])
+def test_runtime_arrays_grow(built, gpu, tmp_path, pageable):
+    """8 packets, then 1025 (past the 1024-entry minimum of the arrays; the
+    pageable pool's bounce buffer grows too) in one process."""
+    frames, out = _run_batch(tmp_path, [(8, 1), (1025, 1)],
+                             {"ODP_AMD_PAGEABLE_POOLS": "parse_pool"} if pageable else None)
+    for (stat, pk), n in zip(out, (8, 1025)):
+        assert stat == (n, 1, int(pageable))
+        assert pk == _batch_model(frames, n)
