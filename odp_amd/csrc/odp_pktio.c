@@ -57,12 +57,12 @@ enum { DRV_LOOP = 1, DRV_PCAP, DRV_NULL };
 enum { ST_OPENED = 0, ST_STARTED, ST_STOPPED };
 
 #define RX_BURST_DEFAULT 4096
-/* staging sets per pktio: one burst staged and classified, one whose GPU
- * delivery is in flight, one being staged */
 /* receive pipeline depth (pktio_recv): classifications and GPU deliveries
  * in flight */
 #define RX_CLS_DEPTH 1
 #define RX_DLV_DEPTH 3
+/* staging sets per pktio: the burst being staged, those whose classification
+ * is in flight and those whose GPU delivery is */
 #define RX_SETS (1 + RX_CLS_DEPTH + RX_DLV_DEPTH)
 /* in-place loop bursts: offsets from the pinned arena's base stay below the
  * kernel's out-of-range offset */
@@ -185,8 +185,8 @@ typedef struct {
 	odp_queue_t loopq;
 	size_t fbuf_bytes;      /* frame store size incl. 64 B of zero padding */
 	int fbuf_pinned;        /* page-locked: the GPU reads frames in place */
-	/* GPU bursts: two staging sets, so one burst is classified while the
-	 * previous one is delivered (pipelined receive) */
+	/* GPU bursts: RX_SETS staging sets, so one burst is staged while older
+	 * ones are classified and delivered (pipelined receive, pktio_recv) */
 	rx_set_t rs[RX_SETS];
 	int cur;                /* set the next burst is staged into */
 	/* receive chain: the control plane's table (per generation), the pools
@@ -213,10 +213,8 @@ static void tx_free(rt_pktio_t *e);
 static void fbuf_free(rt_pktio_t *e);
 static int rx_finish(rt_pktio_t *e, rx_set_t *s, odp_packet_t out[], int max_out);
 static int rx_dlv_end(rt_pktio_t *e, rx_set_t *s, odp_packet_t out[], int max_out);
-static rx_set_t *rx_age(rt_pktio_t *e, int k);
 static int stage_reserve(rx_set_t *s, uint32_t n, size_t bytes);
 static int rxc_loop_stage_ok(rt_pktio_t *e, rx_set_t *s, uint32_t max);
-static int loop_stage_hdrs(rt_pktio_t *e, rx_set_t *s, uint32_t n);
 
 static rt_pktio_t PK[RT_MAX_PKTIO];
 static odp_spinlock_t pk_lock;
@@ -232,6 +230,18 @@ uint32_t rt_gpu_index(void)
 	const char *e = getenv("ODP_AMD_GPU");
 
 	return e ? (uint32_t)atoi(e) : 0u;
+}
+
+/* An on/off environment switch (on unless its value starts with '0'), read
+ * once into *cached (-1 before). */
+static int env_switch(const char *name, int *cached)
+{
+	if (*cached < 0) {
+		const char *v = getenv(name);
+
+		*cached = !(v && v[0] == '0');
+	}
+	return *cached;
 }
 
 static uint32_t rx_burst(void)
@@ -422,8 +432,8 @@ out:
 		/* page-locked frame store: the GPU reads the bursts' header windows
 		 * in place (zero copy, mi_cls_classify_host) and no staging copy is
 		 * made.  ODP_AMD_RX_INPLACE=0 keeps the staged copies (A/B runs). */
-		const char *v = getenv("ODP_AMD_RX_INPLACE");
-		uint8_t *pb = v && v[0] == '0' ? NULL : mi_cls_host_alloc(used_b + 64);
+		int in_place = -1;   /* per load: not cached */
+		uint8_t *pb = env_switch("ODP_AMD_RX_INPLACE", &in_place) ? mi_cls_host_alloc(used_b + 64) : NULL;
 
 		e->fbuf_bytes = used_b + 64;
 		if (pb) {
@@ -1199,8 +1209,6 @@ static void apply_layer(mi_cls_result_t *r, odp_proto_layer_t layer)
 	}
 }
 
-/* Enqueue a run of classified packets (_odp_cos_enq,
- * odp_classification_internal.h:171-201) */
 /* Queue slot of dst inside the CoS (_odp_cos_queue_idx,
  * odp_classification_internal.h:49-65): 0 for a single-queue CoS. */
 static uint32_t cos_slot_of(uint32_t cos_index, odp_queue_t dst)
@@ -1279,6 +1287,20 @@ static void cos_vector_enq(odp_queue_t queue, odp_packet_t pk[], int num, uint32
 	}
 }
 
+/* The plain enqueue of pk[0..num) to q: the packets the queue did not take
+ * (all of them for an invalid queue) are freed.  Returns how many it took. */
+static inline int rx_enq_plain(odp_queue_t q, odp_packet_t pk[], int num)
+{
+	int r = q == ODP_QUEUE_INVALID ? -1
+		: odp_queue_enq_multi(q, (const odp_event_t *)(void *)pk, num);
+
+	if (r < 0)
+		r = 0;
+	if (r != num)
+		odp_packet_free_multi(&pk[r], num - r);
+	return r;
+}
+
 /* One enqueue run (equal dst_queue and cos): _odp_cos_enq
  * (odp_classification_internal.h:142-167).  Single packets and CoS without
  * packet vectors take the plain enqueue -- to odp_queue_aggr(dst, 0) for a
@@ -1295,19 +1317,98 @@ static void cos_enq_run(odp_packet_t pk[], int num)
 	const int std = odp_amd_cls_cos_enq_mode(cos, &vpool, &vmax, &use_aggr);
 
 	if (num < 2 || std != 0) {
-		odp_queue_t q = use_aggr ? odp_queue_aggr(dst, 0) : dst;
-		int r = q == ODP_QUEUE_INVALID ? -1
-			: odp_queue_enq_multi(q, (const odp_event_t *)(void *)pk, num);
+		const int r = rx_enq_plain(use_aggr ? odp_queue_aggr(dst, 0) : dst, pk, num);
 
-		if (r < 0)
-			r = 0;
-		if (r != num)
-			odp_packet_free_multi(&pk[r], num - r);
 		odp_amd_cls_queue_stats_add(cos, cos_slot_of(cos, dst), (uint64_t)r,
 					    (uint64_t)(num - r));
 		return;
 	}
 	cos_vector_enq(dst, pk, num, cos, vpool, vmax);
+}
+
+/* One enqueue per queue group (rx_enqueue, rx_dlv_end, rxc_end): the
+ * group's packets pk[0..num), in arrival order, go to q with one call, and
+ * the queue statistics are kept as per run of the reference (_odp_cos_enq):
+ * per CoS of the queue, cos[k] being the CoS of pk[k] -- the first packets
+ * the queue took counted as enqueued, the rest (freed) as discards. */
+static inline void rx_enq_group(odp_queue_t q, odp_packet_t pk[], const uint8_t cos[], int num)
+{
+	const int r = rx_enq_plain(q, pk, num);
+	uint64_t ok[256], bad[256];
+	uint8_t seen[256], cl[256];
+	int ncos = 0;
+
+	/* by stretches of one CoS [k, e): most groups are a single one */
+	for (int k = 0, e; k < num; k = e) {
+		const uint32_t c = cos[k];
+
+		for (e = k + 1; e < num && cos[e] == c; e++)
+			;
+		const int took = r <= k ? 0 : (r < e ? r : e) - k;
+
+		if (k == 0) {
+			if (e == num) {
+				odp_amd_cls_queue_stats_add(c, cos_slot_of(c, q), (uint64_t)took,
+							    (uint64_t)(num - took));
+				return;
+			}
+			memset(seen, 0, sizeof(seen));
+		}
+		if (!seen[c]) {
+			seen[c] = 1;
+			cl[ncos++] = (uint8_t)c;
+			ok[c] = 0;
+			bad[c] = 0;
+		}
+		ok[c] += (uint64_t)took;
+		bad[c] += (uint64_t)(e - k - took);
+	}
+	for (int k = 0; k < ncos; k++)
+		odp_amd_cls_queue_stats_add(cl[k], cos_slot_of(cl[k], q), ok[cl[k]], bad[cl[k]]);
+}
+
+/* The queue groups of a burst: every queue seen so far, found through an
+ * open-addressing table. */
+#define RX_GROUP_MAXQ 64
+#define RX_GROUP_HASH 256      /* slots: queue -> group */
+typedef struct {
+	odp_queue_t q[RX_GROUP_MAXQ];
+	uint8_t slot[RX_GROUP_HASH];   /* group + 1, 0 empty */
+	int n;
+} rx_qgroups_t;
+
+/* Group of queue q, added when new; -1 when it would be one more than
+ * RX_GROUP_MAXQ. */
+static inline int rx_qgroup_of(rx_qgroups_t *g, odp_queue_t q)
+{
+	/* top 8 bits: RX_GROUP_HASH slots */
+	uint32_t sl = (uint32_t)(((uint64_t)(uintptr_t)q * 0x9E3779B97F4A7C15ull) >> 56);
+
+	while (g->slot[sl] && g->q[g->slot[sl] - 1] != q)
+		sl = (sl + 1) & (RX_GROUP_HASH - 1);
+	if (!g->slot[sl]) {
+		if (g->n == RX_GROUP_MAXQ)
+			return -1;
+		g->q[g->n] = q;
+		g->slot[sl] = (uint8_t)++g->n;
+	}
+	return g->slot[sl] - 1;
+}
+
+/* Whether a CoS's runs take the plain enqueue (no packet vectors, no
+ * aggregator), looked up once per burst: mode[] is 1 plain, 0 not, -1 not
+ * looked up yet. */
+static inline int rx_cos_plain(int8_t mode[256], uint32_t cos)
+{
+	if (mode[cos] < 0) {
+		odp_pool_t vp = ODP_POOL_INVALID;
+		uint32_t vmax = 0;
+		int aggr = 0;
+		const int std = odp_amd_cls_cos_enq_mode(cos, &vp, &vmax, &aggr);
+
+		mode[cos] = std > 0 && !aggr;
+	}
+	return mode[cos];
 }
 
 /* The host's staging of n loop packets already in s->pk: lengths, pools,
@@ -1480,12 +1581,7 @@ static int rx_pipeline(void)
 {
 	static int on = -1;
 
-	if (on < 0) {
-		const char *v = getenv("ODP_AMD_RX_PIPELINE");
-
-		on = !(v && v[0] == '0');
-	}
-	return on;
+	return env_switch("ODP_AMD_RX_PIPELINE", &on);
 }
 
 static void rx_drop(rt_pktio_t *e, rx_set_t *s, int rc)
@@ -1522,126 +1618,105 @@ static int rx_classify(rt_pktio_t *e, rx_set_t *s, int pipe)
 	return 0;
 }
 
-/* The host steps of loopback_recv / pcapif_recv_pkt for frames [lo, hi) of
- * set s (loop.c:253-384, pcap.c:299-352; _odp_packet_parse_common's result
- * applied at the pktio's layer, _odp_cls_classify_packet's outcome, the
- * packet in its final pool, _odp_pktio_packet_to_pool): s->pk[i] becomes the
- * packet to deliver, or ODP_PACKET_INVALID.  (Preparing chunks of a burst on
- * helper threads measured slower -- 14.3 -> 6.4 Mpkt/s with four helpers,
- * profiles/r03g_rx_helpers_ab.txt: each packet's header line then moves between cores
- * on its way to the queue and the consumer -- so one thread does it.) */
-static void rx_prepare_each(rt_pktio_t *e, rx_set_t *s, int lo, int hi, rx_cnt_t *c)
+/* What becomes of one received frame (loop.c:311-337, pcap.c:299-352). */
+typedef enum {
+	RX_PARSE_DROP,    /* the parser drops it: an error */
+	RX_COS_DROP,      /* its CoS drops it: no counter */
+	RX_COS_DISCARD,   /* no CoS takes it (classify < 0, or back to the loop): a discard */
+	RX_DELIVER        /* delivered, as a packet of *pool */
+} rx_verdict_t;
+
+/* A frame's record as the pktio's parse layer leaves it (apply_layer); at
+ * layer NONE, where nothing was classified, all zero with no CoS. */
+static inline void rx_record(const rt_pktio_t *e, const mi_cls_result_t *rec, mi_cls_result_t *r)
 {
-	const odp_proto_layer_t layer = e->parse_layer;
-
-	for (int i = lo; i < hi; i++) {
-		mi_cls_result_t r;
-		odp_packet_t pkt = e->drv == DRV_LOOP ? s->pk[i] : ODP_PACKET_INVALID;
-		uint32_t len = s->slen[i];
-
-		s->pk[i] = ODP_PACKET_INVALID;
-		if (i + 16 < hi)    /* records written by the GPU: not in the CPU caches */
-			__builtin_prefetch(&s->res[i + 16]);
-		if (i + 8 < hi) {   /* frames read in place are cold in the CPU caches */
-			const uint8_t *nf = s->base + s->soff[i + 8];
-			const uint32_t nl = s->slen[i + 8];
-
-			for (uint32_t b = 0; b < nl; b += 64)
-				__builtin_prefetch(nf + b);
-		}
-		if (layer != ODP_PROTO_LAYER_NONE) {
-			r = s->res[i];
-			apply_layer(&r, layer);
-			if (r.err || r.outcome == MI_CLS_OUT_PARSE_DROP)
-				c->in_errors++;
-			if (r.outcome == MI_CLS_OUT_PARSE_DROP) {
-				odp_packet_free(pkt);
-				continue;
-			}
-		} else {
-			memset(&r, 0, sizeof(r));
-			r.cos = 0xff;
-		}
-		odp_pool_t pool = e->pool;
-
-		if (e->cls_enabled) {
-			if (r.outcome == MI_CLS_OUT_DISCARD || r.outcome == MI_CLS_OUT_LOOP)
-				c->in_discards++;
-			if (r.outcome != MI_CLS_OUT_ENQ) {
-				odp_packet_free(pkt);
-				continue;
-			}
-			odp_pool_t cp = odp_amd_cls_pool_of(r.cos);
-
-			if (cp != ODP_POOL_INVALID)
-				pool = cp;
-		}
-		/* packet in the final pool (_odp_pktio_packet_to_pool) */
-		if (pkt == ODP_PACKET_INVALID) {
-			const uint64_t ta = rx_prof > 0 ? __rdtsc() : 0;
-
-			pkt = odp_packet_alloc(pool, len);
-			if (pkt == ODP_PACKET_INVALID) {
-				if (e->cls_enabled)
-					c->in_discards++;
-				continue;
-			}
-			const uint64_t tb = rx_prof > 0 ? __rdtsc() : 0;
-
-			memcpy(odp_packet_data(pkt), s->base + s->soff[i], len);
-			if (rx_prof > 0) {
-				e->prof[6] += tb - ta;
-				e->prof[7] += __rdtsc() - tb;
-			}
-		} else if (odp_packet_pool(pkt) != pool) {
-			odp_packet_t np = odp_packet_alloc(pool, len);
-
-			if (np == ODP_PACKET_INVALID) {
-				odp_packet_free(pkt);
-				c->in_discards++;
-				continue;
-			}
-			pkt_hdr_t *sh = rt_pkt_hdr(pkt);
-
-			memcpy(odp_packet_data(np), sh->head + sh->data_off, len);
-			rt_pkt_hdr(np)->user_ptr = sh->user_ptr;
-			odp_packet_free(pkt);
-			pkt = np;
-		}
-		pkt_hdr_t *h = rt_pkt_hdr(pkt);
-
-		if (layer != ODP_PROTO_LAYER_NONE) {
-			h->in_flags = r.in_flags;
-			h->err = r.err;
-			h->l2 = 0;
-			h->l3 = r.l3_offset;
-			h->l4 = r.l4_offset;
-		} else {
-			h->in_flags = 0;
-			h->err = 0;
-		}
-		/* packet_parse_reset(.., 1) (loop.c:308): a received packet carries
-		 * no pktout checksum overrides (the GPU deliveries write the whole
-		 * metadata block, this field as 0) */
-		h->tx_ck = 0;
-		h->payload_off = 0;
-		h->lso_flags = 0;
-		h->lso_prof = 0;
-		h->lso_max_payload = 0;
-		h->input = e->hdl;
-		if (!h->err) {
-			c->octets += len;
-			c->packets++;
-		}
-		if (e->cls_enabled) {
-			h->cos = r.cos;
-			h->cls_mark = r.mark;
-			h->dst_queue = odp_amd_cls_queue_of(r.cos, r.queue);
-		}
-		s->pk[i] = pkt;
+	if (e->parse_layer != ODP_PROTO_LAYER_NONE) {
+		*r = *rec;
+		apply_layer(r, e->parse_layer);
+	} else {
+		memset(r, 0, sizeof(*r));
+		r->cos = 0xff;
 	}
 }
 
+/* A burst's cache of the CoS lookups: the pool, the queue of slot 0. */
+typedef struct {
+	odp_pool_t pool[256];
+	odp_queue_t q0[256];
+	uint8_t seen[256];
+} rx_cos_cache_t;
+
+static inline void rx_cos_lookup(rx_cos_cache_t *cc, uint32_t cos)
+{
+	if (!cc->seen[cos]) {
+		cc->seen[cos] = 1;
+		cc->pool[cos] = odp_amd_cls_pool_of(cos);
+		cc->q0[cos] = odp_amd_cls_queue_of(cos, 0);
+	}
+}
+
+/* The verdict on a frame from its record, for every delivery path: *r is
+ * rx_record's, *pool where a delivered frame's packet comes from, its CoS's
+ * pool or else the pktio's (looked up through the burst's cache cc, where
+ * the caller keeps one).  With the classifier off only the parser drops.
+ * Nothing is counted here (rx_count). */
+static inline rx_verdict_t rx_decide(const rt_pktio_t *e, const mi_cls_result_t *rec,
+				     mi_cls_result_t *r, odp_pool_t *pool, rx_cos_cache_t *cc)
+{
+	rx_record(e, rec, r);
+	if (r->outcome == MI_CLS_OUT_PARSE_DROP)
+		return RX_PARSE_DROP;
+	*pool = e->pool;
+	if (e->cls_enabled) {
+		if (r->outcome == MI_CLS_OUT_DISCARD || r->outcome == MI_CLS_OUT_LOOP)
+			return RX_COS_DISCARD;
+		if (r->outcome != MI_CLS_OUT_ENQ)
+			return RX_COS_DROP;
+		odp_pool_t cp;
+
+		if (cc) {
+			rx_cos_lookup(cc, r->cos);
+			cp = cc->pool[r->cos];
+		} else {
+			cp = odp_amd_cls_pool_of(r->cos);
+		}
+		if (cp != ODP_POOL_INVALID)
+			*pool = cp;
+	}
+	return RX_DELIVER;
+}
+
+/* The counters of a verdict: in_errors for a parse drop or any error flag of
+ * the record (loop.c:311-312), in_discards for a CoS discard (loop.c:324-330;
+ * the verdict exists with the classifier on only). */
+static inline void rx_count(rx_verdict_t v, int err, rx_cnt_t *c)
+{
+	if (err || v == RX_PARSE_DROP)
+		c->in_errors++;
+	if (v == RX_COS_DISCARD)
+		c->in_discards++;
+}
+
+/* A delivered frame found no packet (too long for its pool, or the pool ran
+ * short): a discard with the classifier on (loop.c:332-337; off, the
+ * reference's receive stops instead, pcap.c:324-327), and always for a loop
+ * packet `had` that failed to switch pools. */
+static inline void rx_count_no_packet(const rt_pktio_t *e, odp_packet_t had, rx_cnt_t *c)
+{
+	if (e->cls_enabled || had != ODP_PACKET_INVALID)
+		c->in_discards++;
+}
+
+/* Add a delivery's counters to the pktio's. */
+static inline void rx_cnt_flush(rt_pktio_t *e, const rx_cnt_t *c)
+{
+	if (c->in_errors)
+		odp_atomic_add_u64(&e->in_errors, c->in_errors);
+	if (c->in_discards)
+		odp_atomic_add_u64(&e->in_discards, c->in_discards);
+	odp_atomic_add_u64(&e->in_octets, c->octets);
+	odp_atomic_add_u64(&e->in_packets, c->packets);
+}
 
 /* Packet metadata of a delivered frame from its record. */
 static inline void rx_fill(rt_pktio_t *e, pkt_hdr_t *h, const mi_cls_result_t *r, uint32_t len,
@@ -1669,99 +1744,219 @@ static inline void rx_fill(rt_pktio_t *e, pkt_hdr_t *h, const mi_cls_result_t *r
 	}
 }
 
+/* The host steps of loopback_recv / pcapif_recv_pkt for frames [lo, hi) of
+ * set s (loop.c:253-384, pcap.c:299-352; _odp_packet_parse_common's result
+ * applied at the pktio's layer, _odp_cls_classify_packet's outcome, the
+ * packet in its final pool, _odp_pktio_packet_to_pool): s->pk[i] becomes the
+ * packet to deliver, or ODP_PACKET_INVALID.  (Preparing chunks of a burst on
+ * helper threads measured slower -- 14.3 -> 6.4 Mpkt/s with four helpers,
+ * profiles/r03g_rx_helpers_ab.txt: each packet's header line then moves between cores
+ * on its way to the queue and the consumer -- so one thread does it.) */
+static void rx_prepare_each(rt_pktio_t *e, rx_set_t *s, int lo, int hi, rx_cnt_t *c)
+{
+	for (int i = lo; i < hi; i++) {
+		mi_cls_result_t r;
+		odp_packet_t pkt = e->drv == DRV_LOOP ? s->pk[i] : ODP_PACKET_INVALID;
+		uint32_t len = s->slen[i];
+
+		s->pk[i] = ODP_PACKET_INVALID;
+		if (i + 16 < hi)    /* records written by the GPU: not in the CPU caches */
+			__builtin_prefetch(&s->res[i + 16]);
+		if (i + 8 < hi) {   /* frames read in place are cold in the CPU caches */
+			const uint8_t *nf = s->base + s->soff[i + 8];
+			const uint32_t nl = s->slen[i + 8];
+
+			for (uint32_t b = 0; b < nl; b += 64)
+				__builtin_prefetch(nf + b);
+		}
+		odp_pool_t pool;
+		const rx_verdict_t v = rx_decide(e, &s->res[i], &r, &pool, NULL);
+
+		rx_count(v, r.err, c);
+		if (v != RX_DELIVER) {
+			odp_packet_free(pkt);
+			continue;
+		}
+		/* packet in the final pool (_odp_pktio_packet_to_pool) */
+		if (pkt == ODP_PACKET_INVALID) {
+			const uint64_t ta = rx_prof > 0 ? __rdtsc() : 0;
+
+			pkt = odp_packet_alloc(pool, len);
+			if (pkt == ODP_PACKET_INVALID) {
+				rx_count_no_packet(e, pkt, c);
+				continue;
+			}
+			const uint64_t tb = rx_prof > 0 ? __rdtsc() : 0;
+
+			memcpy(odp_packet_data(pkt), s->base + s->soff[i], len);
+			if (rx_prof > 0) {
+				e->prof[6] += tb - ta;
+				e->prof[7] += __rdtsc() - tb;
+			}
+		} else if (odp_packet_pool(pkt) != pool) {
+			odp_packet_t np = odp_packet_alloc(pool, len);
+
+			if (np == ODP_PACKET_INVALID) {
+				rx_count_no_packet(e, pkt, c);
+				odp_packet_free(pkt);
+				continue;
+			}
+			pkt_hdr_t *sh = rt_pkt_hdr(pkt);
+
+			memcpy(odp_packet_data(np), sh->head + sh->data_off, len);
+			rt_pkt_hdr(np)->user_ptr = sh->user_ptr;
+			odp_packet_free(pkt);
+			pkt = np;
+		} else {
+			/* a loop packet delivered in place: packet_parse_reset(.., 1)
+			 * (loop.c:308), a received packet carries no pktout checksum
+			 * or LSO overrides (a fresh packet has none, pkt_init; the GPU
+			 * deliveries write the whole metadata block, these as 0) */
+			pkt_hdr_t *h = rt_pkt_hdr(pkt);
+
+			h->tx_ck = 0;
+			h->payload_off = 0;
+			h->lso_flags = 0;
+			h->lso_prof = 0;
+			h->lso_max_payload = 0;
+		}
+		rx_fill(e, rt_pkt_hdr(pkt), &r, len, c);
+		s->pk[i] = pkt;
+	}
+}
+
+/* A set's delivery scratch (s->tmp): n_cap packets -- those taken from the
+ * pools in bulk, then a queue group's -- followed by one byte per frame -- its
+ * pool bucket or verdict, then its queue group, then a group's CoS values.
+ * rx_tmp_bytes is NULL when there is none. */
+static void rx_tmp_ensure(rx_set_t *s)
+{
+	if (!s->tmp || s->tmp_cap < s->n_cap) {
+		free(s->tmp);
+		s->tmp = malloc(s->n_cap * (sizeof(odp_packet_t) + 1u));
+		s->tmp_cap = s->tmp ? s->n_cap : 0;
+	}
+}
+
+static inline uint8_t *rx_tmp_bytes(const rx_set_t *s)
+{
+	return s->tmp ? (uint8_t *)(void *)(s->tmp + s->tmp_cap) : NULL;
+}
+
+/* The pool buckets of a burst delivered in passes (rx_prepare, rx_dlv_start):
+ * pass 1 finds each delivered frame's bucket and counts it in, pass 2 takes
+ * every bucket's packets from its pool at once, pass 3 hands them out.
+ * Frames of one pool get their packets in arrival order, so when a pool runs
+ * short the same frames go without as frame-by-frame allocation would leave
+ * (pktio/loop.c:332-337); every frame counted in asks for its packet, so
+ * none taken is left over. */
+#define RX_MAX_POOLS 16
+typedef struct {
+	odp_pool_t pool;
+	uint32_t cap;   /* longest frame a packet of it holds (0: not a packet pool) */
+	int pinned;     /* page-locked */
+	int cnt;        /* frames counted in */
+	int base, have; /* its packets: got[base .. base + have) */
+	int used;       /* asked for so far */
+} rx_bucket_t;
+
+typedef struct {
+	rx_bucket_t b[RX_MAX_POOLS];
+	int n;
+} rx_buckets_t;
+
+/* Bucket of a pool, added when new; -1 when all RX_MAX_POOLS are other
+ * pools' (the caller falls back). */
+static inline int rx_bucket_of(rx_buckets_t *bk, odp_pool_t pool)
+{
+	int k = 0;
+
+	while (k < bk->n && bk->b[k].pool != pool)
+		k++;
+	if (k == bk->n) {
+		const rt_pool_t *rp = rt_pool(pool);
+
+		if (k == RX_MAX_POOLS)
+			return -1;
+		bk->b[k].pool = pool;
+		bk->b[k].cap = rp && rp->param.type == ODP_POOL_PACKET ? rp->data_cap : 0u;
+		bk->b[k].pinned = rp && rp->pinned;
+		bk->b[k].cnt = 0;
+		bk->n++;
+	}
+	return k;
+}
+
+/* Take every bucket's packets at once, into got[at ...). */
+static inline void rx_buckets_take(rx_buckets_t *bk, odp_packet_t got[], int at)
+{
+	for (int k = 0; k < bk->n; k++) {
+		rx_bucket_t *b = &bk->b[k];
+
+		b->base = at;
+		b->have = b->cnt ? rt_packet_alloc_raw(b->pool, 0, &got[at], b->cnt) : 0;
+		b->used = 0;
+		at += b->cnt;
+	}
+}
+
+/* The next packet of a bucket, ODP_PACKET_INVALID when its pool ran short. */
+static inline odp_packet_t rx_bucket_next(rx_bucket_t *b, const odp_packet_t got[])
+{
+	const int j = b->used++;
+
+	return j < b->have ? got[b->base + j] : ODP_PACKET_INVALID;
+}
+
 /* rx_prepare for pcap frames: the same steps in three passes, so packets
  * are taken from each pool in bulk and their headers prefetched before they
  * are written (a per-frame odp_packet_alloc spent most of its time on the
- * cold header line).  Pass 1 decides each frame (parse drop, CoS discard, or
- * the pool it goes to), pass 2 takes every pool's packets at once -- frames
- * of one pool get them in arrival order, so when a pool runs short the same
- * frames are discarded as frame-by-frame allocation would -- and pass 3
+ * cold header line).  Pass 1 decides each frame (rx_decide) and counts it
+ * into its pool's bucket, pass 2 takes the buckets' packets, and pass 3
  * initialises the headers, copies the frames and writes the metadata.
  * `slot` (one byte per frame) and `got` (n_cap packets) are the set's
  * delivery scratch; more than RX_MAX_POOLS distinct pools in a burst fall
  * back to rx_prepare_each. */
-#define RX_MAX_POOLS 16
 static void rx_prepare(rt_pktio_t *e, rx_set_t *s, int lo, int hi, rx_cnt_t *c)
 {
-	const odp_proto_layer_t layer = e->parse_layer;
-	uint8_t *slot = s->tmp ? (uint8_t *)(void *)(s->tmp + s->tmp_cap) : NULL;
+	uint8_t *slot = rx_tmp_bytes(s);
 	odp_packet_t *got = s->tmp;
-	struct {
-		odp_pool_t pool;
-		uint32_t cap;
-		int cnt, base, have, used;
-	} pl[RX_MAX_POOLS];
-	int npl = 0;
+	rx_buckets_t bk;
 
 	if (e->drv != DRV_PCAP || !slot) {
 		rx_prepare_each(e, s, lo, hi, c);
 		return;
 	}
+	bk.n = 0;
 	/* pass 1: the decision per frame */
 	for (int i = lo; i < hi; i++) {
 		if (i + 16 < hi)
 			__builtin_prefetch(&s->res[i + 16]);
 		mi_cls_result_t r;
-		const uint32_t len = s->slen[i];
+		odp_pool_t pool;
+		const rx_verdict_t v = rx_decide(e, &s->res[i], &r, &pool, NULL);
 
 		s->pk[i] = ODP_PACKET_INVALID;
 		slot[i] = 0xff;
-		if (layer != ODP_PROTO_LAYER_NONE) {
-			r = s->res[i];
-			apply_layer(&r, layer);
-			if (r.err || r.outcome == MI_CLS_OUT_PARSE_DROP)
-				c->in_errors++;
-			if (r.outcome == MI_CLS_OUT_PARSE_DROP)
-				continue;
-		} else {
-			memset(&r, 0, sizeof(r));
+		rx_count(v, r.err, c);
+		if (v != RX_DELIVER)
+			continue;
+		const int k = rx_bucket_of(&bk, pool);
+
+		if (k < 0) {   /* start over frame by frame */
+			memset(c, 0, sizeof(*c));
+			rx_prepare_each(e, s, lo, hi, c);
+			return;
 		}
-		odp_pool_t pool = e->pool;
-
-		if (e->cls_enabled) {
-			if (r.outcome == MI_CLS_OUT_DISCARD || r.outcome == MI_CLS_OUT_LOOP)
-				c->in_discards++;
-			if (r.outcome != MI_CLS_OUT_ENQ)
-				continue;
-			odp_pool_t cp = odp_amd_cls_pool_of(r.cos);
-
-			if (cp != ODP_POOL_INVALID)
-				pool = cp;
-		}
-		int k = 0;
-
-		while (k < npl && pl[k].pool != pool)
-			k++;
-		if (k == npl) {
-			rt_pool_t *rp = rt_pool(pool);
-
-			if (npl == RX_MAX_POOLS) {   /* start over frame by frame */
-				memset(c, 0, sizeof(*c));
-				rx_prepare_each(e, s, lo, hi, c);
-				return;
-			}
-			pl[k].pool = pool;
-			pl[k].cap = rp && rp->param.type == ODP_POOL_PACKET ? rp->data_cap : 0u;
-			pl[k].cnt = 0;
-			npl++;
-		}
-		if (len > pl[k].cap) {   /* odp_packet_alloc fails: no packet taken */
-			if (e->cls_enabled)
-				c->in_discards++;
+		if (s->slen[i] > bk.b[k].cap) {   /* odp_packet_alloc fails: no packet taken */
+			rx_count_no_packet(e, ODP_PACKET_INVALID, c);
 			continue;
 		}
 		slot[i] = (uint8_t)k;
-		pl[k].cnt++;
+		bk.b[k].cnt++;
 	}
 	/* pass 2: each pool's packets at once */
-	int at = lo;
-
-	for (int k = 0; k < npl; k++) {
-		pl[k].base = at;
-		pl[k].have = pl[k].cnt ? rt_packet_alloc_raw(pl[k].pool, 0, &got[at], pl[k].cnt) : 0;
-		pl[k].used = 0;
-		at += pl[k].cnt;
-	}
+	rx_buckets_take(&bk, got, lo);
 	/* pass 3: headers, frames, metadata */
 	for (int i = lo; i < hi; i++) {
 		if (i + 8 < hi) {   /* frames read in place are cold in the CPU caches */
@@ -1771,19 +1966,17 @@ static void rx_prepare(rt_pktio_t *e, rx_set_t *s, int lo, int hi, rx_cnt_t *c)
 			for (uint32_t b = 0; b < nl; b += 64)
 				__builtin_prefetch(nf + b);
 		}
-		const int k = slot[i];
-
-		if (k == 0xff)
+		if (slot[i] == 0xff)
 			continue;
-		const int j = pl[k].used++;
+		rx_bucket_t *b = &bk.b[slot[i]];
+		const odp_packet_t pkt = rx_bucket_next(b, got);
 
-		if (j >= pl[k].have) {   /* the pool ran short */
-			if (e->cls_enabled)
-				c->in_discards++;
+		if (pkt == ODP_PACKET_INVALID) {   /* the pool ran short */
+			rx_count_no_packet(e, ODP_PACKET_INVALID, c);
 			continue;
 		}
-		if (j + 4 < pl[k].have) {   /* a later packet of this pool: its header */
-			const pkt_hdr_t *nh = rt_pkt_hdr(got[pl[k].base + j + 4]);
+		if (b->used + 3 < b->have) {   /* a later packet of this pool: its header */
+			const pkt_hdr_t *nh = rt_pkt_hdr(got[b->base + b->used + 3]);
 
 			/* the buffer follows the 64-B aligned header (odp_rt.c pool
 			 * layout): its first data line, without reading the header */
@@ -1791,17 +1984,10 @@ static void rx_prepare(rt_pktio_t *e, rx_set_t *s, int lo, int hi, rx_cnt_t *c)
 			__builtin_prefetch((const uint8_t *)nh + ((sizeof(pkt_hdr_t) + 63u) & ~(size_t)63u) +
 					   RT_PKT_HEADROOM, 1);
 		}
-		const odp_packet_t pkt = got[pl[k].base + j];
 		const uint32_t len = s->slen[i];
 		mi_cls_result_t r;
 
-		if (layer != ODP_PROTO_LAYER_NONE) {
-			r = s->res[i];
-			apply_layer(&r, layer);
-		} else {
-			memset(&r, 0, sizeof(r));
-			r.cos = 0xff;
-		}
+		rx_record(e, &s->res[i], &r);
 		const uint64_t ta = rx_prof > 0 ? __rdtsc() : 0;
 
 		rt_packet_init(pkt, len);
@@ -1817,7 +2003,19 @@ static void rx_prepare(rt_pktio_t *e, rx_set_t *s, int lo, int hi, rx_cnt_t *c)
 	}
 }
 
-/* Enqueue the delivered packets pk[0..n) in arrival order.  _odp_cls_enq
+/* Classifier off: the delivered packets pk[0..n) go to the caller's out[]
+ * (at most max_out, the rest are freed).  Returns how many it got. */
+static inline int rx_to_caller(const odp_packet_t pk[], int n, odp_packet_t out[], int max_out)
+{
+	const int num_rx = n < max_out ? n : (max_out > 0 ? max_out : 0);
+
+	if (num_rx)
+		memcpy(out, pk, (size_t)num_rx * sizeof(odp_packet_t));
+	odp_packet_free_multi(&pk[num_rx], n - num_rx);
+	return num_rx;
+}
+
+/* Enqueue the delivered packets pk[0..n) of set s in arrival order.  _odp_cls_enq
  * (odp_classification_internal.h:171-201) enqueues runs of equal
  * (dst_queue, CoS); when every run of the burst takes the plain enqueue (no
  * packet vectors, no aggregator), the runs of one queue are joined into one
@@ -1827,58 +2025,36 @@ static void rx_prepare(rt_pktio_t *e, rx_set_t *s, int lo, int hi, rx_cnt_t *c)
  * statistics are kept as per run.  Runs of CoS with packet vectors or
  * aggregators keep the reference's per-run form (their vector boundaries
  * depend on it). */
-#define RX_GROUP_MAXQ 64
-#define RX_GROUP_HASH 256      /* open-addressing slots: queue -> group */
-static inline uint32_t rx_qhash(odp_queue_t q)
+static void rx_enqueue(rx_set_t *s, odp_packet_t pk[], int n)
 {
-	const uint64_t x = (uint64_t)(uintptr_t)q * 0x9E3779B97F4A7C15ull;
+	odp_packet_t *tmp = s->tmp;
+	uint8_t *gidx = rx_tmp_bytes(s);
+	rx_qgroups_t g;
+	int cnt[RX_GROUP_MAXQ], fill[RX_GROUP_MAXQ];
+	int plain = 1;
+	int8_t mode_of_cos[256];
 
-	return (uint32_t)(x >> 56);   /* 8 bits: RX_GROUP_HASH slots */
-}
-
-static void rx_enqueue(odp_packet_t pk[], int n, odp_packet_t *tmp, uint8_t *gidx)
-{
-	struct {
-		odp_queue_t q;
-		int cnt, fill;
-	} g[RX_GROUP_MAXQ];
-	int ng = 0, plain = 1;
-	int8_t mode_of_cos[256];   /* 1 plain, 0 not, -1 unknown */
-	uint8_t slot_grp[RX_GROUP_HASH];   /* group + 1, 0 empty */
-
+	if (!tmp) {   /* no scratch to sort in: packet by packet */
+		for (int i = 0; i < n; i++)
+			cos_enq_run(&pk[i], 1);
+		return;
+	}
 	memset(mode_of_cos, -1, sizeof(mode_of_cos));
-	memset(slot_grp, 0, sizeof(slot_grp));
+	memset(g.slot, 0, sizeof(g.slot));
+	g.n = 0;
 	for (int i = 0; i < n; i++) {
-		pkt_hdr_t *h = rt_pkt_hdr(pk[i]);
-		const uint32_t cos = h->cos & 0xffu;
+		const pkt_hdr_t *h = rt_pkt_hdr(pk[i]);
+		const int known = g.n;
+		const int k = rx_cos_plain(mode_of_cos, h->cos & 0xffu) ? rx_qgroup_of(&g, h->dst_queue) : -1;
 
-		if (mode_of_cos[cos] < 0) {
-			odp_pool_t vp = ODP_POOL_INVALID;
-			uint32_t vmax = 0;
-			int aggr = 0;
-			const int std = odp_amd_cls_cos_enq_mode(cos, &vp, &vmax, &aggr);
-
-			mode_of_cos[cos] = std > 0 && !aggr;
-		}
-		if (!mode_of_cos[cos]) {
+		if (k < 0) {   /* vectors, an aggregator, or more than RX_GROUP_MAXQ queues */
 			plain = 0;
 			break;
 		}
-		uint32_t sl = rx_qhash(h->dst_queue);
-
-		while (slot_grp[sl] && g[slot_grp[sl] - 1].q != h->dst_queue)
-			sl = (sl + 1) & (RX_GROUP_HASH - 1);
-		if (!slot_grp[sl]) {
-			if (ng == RX_GROUP_MAXQ) {
-				plain = 0;
-				break;
-			}
-			g[ng].q = h->dst_queue;
-			g[ng].cnt = 0;
-			slot_grp[sl] = (uint8_t)++ng;
-		}
-		gidx[i] = (uint8_t)(slot_grp[sl] - 1);
-		g[slot_grp[sl] - 1].cnt++;
+		if (k == known)
+			cnt[k] = 0;
+		gidx[i] = (uint8_t)k;
+		cnt[k]++;
 	}
 	if (!plain) {
 		/* the reference's form: one enqueue per run */
@@ -1902,46 +2078,21 @@ static void rx_enqueue(odp_packet_t pk[], int n, odp_packet_t *tmp, uint8_t *gid
 	/* counting sort by queue, stable: each group's packets in arrival order */
 	int at = 0;
 
-	for (int k = 0; k < ng; k++) {
-		g[k].fill = at;
-		at += g[k].cnt;
+	for (int k = 0; k < g.n; k++) {
+		fill[k] = at;
+		at += cnt[k];
 	}
 	for (int i = 0; i < n; i++)
-		tmp[g[gidx[i]].fill++] = pk[i];
+		tmp[fill[gidx[i]]++] = pk[i];
+	/* (the group bytes are done with: each group's CoS values go there) */
 	at = 0;
-	for (int k = 0; k < ng; k++) {
+	for (int k = 0; k < g.n; k++) {
 		odp_packet_t *gp = tmp + at;
-		const int num = g[k].cnt;
-		int r = odp_queue_enq_multi(g[k].q, (const odp_event_t *)(void *)gp, num);
 
-		at += num;
-		if (r < 0)
-			r = 0;
-		if (r != num)
-			odp_packet_free_multi(&gp[r], num - r);
-		/* queue statistics as per run of the reference: per CoS of the queue */
-		int done = 0;
-
-		for (int j = 0; j < num && done < num; j++) {
-			const uint32_t cos = rt_pkt_hdr(gp[j])->cos;
-			int first = 1;
-
-			for (int t = 0; t < j && first; t++)
-				first = rt_pkt_hdr(gp[t])->cos != cos;
-			if (!first)
-				continue;
-			uint64_t ok = 0, bad = 0;
-
-			for (int t = j; t < num; t++)
-				if (rt_pkt_hdr(gp[t])->cos == cos) {
-					if (t < r)
-						ok++;
-					else
-						bad++;
-				}
-			done += (int)(ok + bad);
-			odp_amd_cls_queue_stats_add(cos, cos_slot_of(cos, g[k].q), ok, bad);
-		}
+		for (int j = 0; j < cnt[k]; j++)
+			gidx[j] = (uint8_t)rt_pkt_hdr(gp[j])->cos;
+		rx_enq_group(g.q[k], gp, gidx, cnt[k]);
+		at += cnt[k];
 	}
 }
 
@@ -1950,56 +2101,28 @@ static int gpu_deliver_on(void)
 {
 	static int on = -1;
 
-	if (on < 0) {
-		const char *v = getenv("ODP_AMD_RX_GPU_DELIVER");
-
-		on = !(v && v[0] == '0');
-	}
-	return on;
+	return env_switch("ODP_AMD_RX_GPU_DELIVER", &on);
 }
 
 /* Enqueue the grouped packets of a GPU delivery: group g (queue gq[g]) holds
- * entries perm[at .. at + gcnt[g]) in arrival order; queue statistics per
- * CoS of the queue as per run of the reference. */
-static void rx_enqueue_groups(rx_set_t *s, const odp_queue_t *gq, int ng, odp_packet_t *tmp)
+ * entries perm[at .. at + gcnt[g]) in arrival order. */
+static void rx_enqueue_groups(rx_set_t *s)
 {
+	uint8_t *cos = rx_tmp_bytes(s);
 	uint32_t at = 0;
 
-	for (int g = 0; g < ng; g++) {
+	for (int g = 0; g < s->ng; g++) {
 		const uint32_t num = s->gcnt[g];
-		uint64_t ok[256], bad[256];
-		uint8_t seen[256];
-		int ncos = 0;
-		uint8_t cl[256];
 
 		if (!num)
 			continue;
-		for (uint32_t k = 0; k < num; k++)
-			tmp[k] = s->ent[s->perm[at + k]];
-		int r = odp_queue_enq_multi(gq[g], (const odp_event_t *)(void *)tmp, (int)num);
-
-		if (r < 0)
-			r = 0;
-		if ((uint32_t)r != num)
-			odp_packet_free_multi(&tmp[r], (int)num - r);
-		memset(seen, 0, sizeof(seen));
 		for (uint32_t k = 0; k < num; k++) {
-			const uint32_t cos = s->res[s->dlv[s->perm[at + k]].rec].cos;
+			const uint32_t j = s->perm[at + k];
 
-			if (!seen[cos]) {
-				seen[cos] = 1;
-				cl[ncos++] = (uint8_t)cos;
-				ok[cos] = 0;
-				bad[cos] = 0;
-			}
-			if (k < (uint32_t)r)
-				ok[cos]++;
-			else
-				bad[cos]++;
+			s->tmp[k] = s->ent[j];
+			cos[k] = s->res[s->dlv[j].rec].cos;
 		}
-		for (int k = 0; k < ncos; k++)
-			odp_amd_cls_queue_stats_add(cl[k], cos_slot_of(cl[k], gq[g]), ok[cl[k]],
-						    bad[cl[k]]);
+		rx_enq_group(s->gq[g], s->tmp, cos, (int)num);
 		at += num;
 	}
 }
@@ -2017,142 +2140,102 @@ static void rx_enqueue_groups(rx_set_t *s, const odp_queue_t *gq, int ng, odp_pa
  * needs the host path (a destination pool not page-locked, more than
  * RX_MAX_POOLS pools, frames the GPU cannot address) -- nothing has been
  * done then. */
+_Static_assert(RX_GROUP_MAXQ <= MI_CLS_DLV_GROUPS && RX_MAX_POOLS <= 0x10, "delivery codes");
 static int rx_dlv_start(rt_pktio_t *e, rx_set_t *s, rx_cnt_t *c)
 {
 	const odp_proto_layer_t layer = e->parse_layer;
-	uint8_t *slot = s->tmp ? (uint8_t *)(void *)(s->tmp + s->tmp_cap) : NULL;
+	uint8_t *slot = rx_tmp_bytes(s);
 	odp_packet_t *got = s->tmp;
-	struct {
-		odp_pool_t pool;
-		uint32_t cap;
-		int cnt, base, have, used;
-	} pl[RX_MAX_POOLS];
-	int npl = 0;
-	enum { A_NONE = 0xff, A_INPLACE = 0xfe };   /* else: index of the pool */
+	rx_buckets_t bk;
+	/* a frame's byte from pass 1 to pass 3: the bucket of its pool, or */
+	enum {
+		A_INPLACE = 0x10,   /* a loop packet stays in its own buffer */
+		A_TOO_LONG,         /* longer than a packet of its pool: no packet */
+		A_VERDICT = 0x20,   /* + its rx_verdict_t: not delivered */
+		A_ERR = 0x80        /* with any of them: the record has error flags */
+	};
 
 	if (!gpu_deliver_on() || !s->dlv_pinned || !slot || layer == ODP_PROTO_LAYER_NONE ||
 	    !mi_cls_host_mapped(s->base))
 		return -1;
 	const uint64_t td0 = prof_ns();
 	s->dgen = odp_amd_cls_generation();
-	/* per-burst caches of the CoS lookups (pool, queue of slot 0) */
-	odp_pool_t cpool[256];
-	odp_queue_t cq0[256];
-	uint8_t cseen[256];
-
-	memset(cseen, 0, sizeof(cseen));
-#define COS_SEEN(cos)                                                                  \
-	do {                                                                           \
-		if (!cseen[cos]) {                                                     \
-			cseen[cos] = 1;                                                \
-			cpool[cos] = odp_amd_cls_pool_of(cos);                         \
-			cq0[cos] = odp_amd_cls_queue_of(cos, 0);                       \
-		}                                                                      \
-	} while (0)
 	/* pass 1: the decision per frame, no side effects yet */
+	rx_cos_cache_t cc;
+
+	memset(cc.seen, 0, sizeof(cc.seen));
+	bk.n = 0;
 	for (int i = 0; i < s->n; i++) {
-		mi_cls_result_t r = s->res[i];
-		odp_pool_t pool = e->pool;
+		mi_cls_result_t r;
+		odp_pool_t pool;
+		uint8_t a;
 
 		if (i + 16 < s->n)
 			__builtin_prefetch(&s->res[i + 16]);
-		slot[i] = A_NONE;
-		apply_layer(&r, layer);
-		if (r.outcome == MI_CLS_OUT_PARSE_DROP)
-			continue;
-		if (e->cls_enabled) {
-			if (r.outcome != MI_CLS_OUT_ENQ)
-				continue;
-			COS_SEEN(r.cos);
-			if (cpool[r.cos] != ODP_POOL_INVALID)
-				pool = cpool[r.cos];
-		}
-		if (e->drv == DRV_LOOP && (odp_pool_t)(uintptr_t)s->ppool[i] == pool) {
+		const rx_verdict_t v = rx_decide(e, &s->res[i], &r, &pool, &cc);
+
+		if (v != RX_DELIVER) {
+			a = (uint8_t)(A_VERDICT + v);
+		} else if (e->drv == DRV_LOOP && (odp_pool_t)(uintptr_t)s->ppool[i] == pool) {
 			/* the GPU writes the packet's own header */
 			if (!rt_pool(pool)->pinned)
 				return -1;
-			slot[i] = A_INPLACE;
-			continue;
-		}
-		int k = 0;
+			a = A_INPLACE;
+		} else {
+			const int k = rx_bucket_of(&bk, pool);
 
-		while (k < npl && pl[k].pool != pool)
-			k++;
-		if (k == npl) {
-			rt_pool_t *rp = rt_pool(pool);
-
-			if (npl == RX_MAX_POOLS || !rp || !rp->pinned)
+			if (k < 0 || !bk.b[k].pinned)
 				return -1;
-			pl[k].pool = pool;
-			pl[k].cap = rp->param.type == ODP_POOL_PACKET ? rp->data_cap : 0u;
-			pl[k].cnt = 0;
-			npl++;
+			if (s->slen[i] > bk.b[k].cap) {   /* odp_packet_alloc fails */
+				a = A_TOO_LONG;
+			} else {
+				a = (uint8_t)k;
+				bk.b[k].cnt++;
+			}
 		}
-		if (s->slen[i] > pl[k].cap)   /* odp_packet_alloc fails: discarded */
-			continue;
-		slot[i] = (uint8_t)k;
-		pl[k].cnt++;
+		slot[i] = r.err ? a | A_ERR : a;
 	}
 	/* pass 2: each pool's packets at once */
-	int at = 0;
-
-	for (int k = 0; k < npl; k++) {
-		pl[k].base = at;
-		pl[k].have = pl[k].cnt ? rt_packet_alloc_raw(pl[k].pool, 0, &got[at], pl[k].cnt) : 0;
-		pl[k].used = 0;
-		at += pl[k].cnt;
-	}
+	rx_buckets_take(&bk, got, 0);
 	/* pass 3: counters, drops, entries (queue groups: every plain-enqueue
 	 * queue of the burst, at most MI_CLS_DLV_GROUPS) */
-	odp_queue_t gq[MI_CLS_DLV_GROUPS];
-	int ng = 0, grouped = e->cls_enabled, nold = 0;
+	rx_qgroups_t g;
+	int grouped = e->cls_enabled, nold = 0;
 	int8_t mode_of_cos[256];
-	uint8_t slot_grp[RX_GROUP_HASH];
 	uint32_t ne = 0;
 
 	memset(mode_of_cos, -1, sizeof(mode_of_cos));
-	memset(slot_grp, 0, sizeof(slot_grp));
+	memset(g.slot, 0, sizeof(g.slot));
+	g.n = 0;
 	for (int i = 0; i < s->n; i++) {
-		mi_cls_result_t r = s->res[i];
+		const mi_cls_result_t *rec = &s->res[i];   /* (its CoS and queue: any layer's) */
 		const uint32_t len = s->slen[i];
-		const int k = slot[i];
+		const int a = slot[i] & ~A_ERR, err = slot[i] & A_ERR;
 		odp_packet_t pkt = e->drv == DRV_LOOP ? s->pk[i] : ODP_PACKET_INVALID;
 
 		s->pk[i] = ODP_PACKET_INVALID;
-		apply_layer(&r, layer);
-		if (r.err || r.outcome == MI_CLS_OUT_PARSE_DROP)
-			c->in_errors++;
-		if (r.outcome == MI_CLS_OUT_PARSE_DROP) {
-			odp_packet_free(pkt);
-			continue;
-		}
-		if (e->cls_enabled && (r.outcome == MI_CLS_OUT_DISCARD || r.outcome == MI_CLS_OUT_LOOP))
-			c->in_discards++;
-		if (e->cls_enabled && r.outcome != MI_CLS_OUT_ENQ) {
+		rx_count(a >= A_VERDICT ? (rx_verdict_t)(a - A_VERDICT) : RX_DELIVER, err, c);
+		if (a >= A_VERDICT) {
 			odp_packet_free(pkt);
 			continue;
 		}
 		uint8_t fl = MI_CLS_DLV_FRESH | MI_CLS_DLV_COPY;
 		odp_packet_t dst;
 
-		if (k == A_INPLACE) {
+		if (a == A_INPLACE) {
 			dst = pkt;
 			fl = 0;
-		} else if (k == A_NONE || pl[k].used >= pl[k].have) {
-			/* too long for the pool, or the pool ran short (a loop
-			 * packet's failed pool switch is a discard either way) */
-			if (k != A_NONE)
-				pl[k].used++;
-			if (e->cls_enabled || pkt != ODP_PACKET_INVALID)
-				c->in_discards++;
-			odp_packet_free(pkt);
-			continue;
 		} else {
-			dst = got[pl[k].base + pl[k].used++];
+			dst = a == A_TOO_LONG ? ODP_PACKET_INVALID : rx_bucket_next(&bk.b[a], got);
+			if (dst == ODP_PACKET_INVALID) {   /* too long, or the pool ran short */
+				rx_count_no_packet(e, pkt, c);
+				odp_packet_free(pkt);
+				continue;
+			}
 			if (pkt != ODP_PACKET_INVALID)
 				s->old[nold++] = pkt;   /* freed once the GPU copied it */
 		}
-		if (!r.err) {
+		if (!err) {
 			c->octets += len;
 			c->packets++;
 		}
@@ -2160,42 +2243,27 @@ static int rx_dlv_start(rt_pktio_t *e, rx_set_t *s, rx_cnt_t *c)
 		uint8_t qid = 0xff;
 
 		d->meta = (uint64_t)(uintptr_t)&rt_pkt_hdr(dst)->meta;
-		d->data_off = k == A_INPLACE ? s->pdoff[i] : RT_PKT_HEADROOM;
+		d->data_off = a == A_INPLACE ? s->pdoff[i] : RT_PKT_HEADROOM;
 		/* the metadata line is written whole: a packet received in place
 		 * keeps its user pointer (read with its headroom at staging) */
-		d->user_ptr = k == A_INPLACE ? (uint64_t)(uintptr_t)s->pup[i] : 0u;
+		d->user_ptr = a == A_INPLACE ? (uint64_t)(uintptr_t)s->pup[i] : 0u;
 		d->dst_queue = 0;
 		d->src = s->soff[i];
 		d->rec = (uint32_t)i;
 		d->len = (uint16_t)len;
 		if (e->cls_enabled) {
-			const odp_queue_t q = r.queue == 0 ? cq0[r.cos] : odp_amd_cls_queue_of(r.cos, r.queue);
+			const odp_queue_t q = rec->queue == 0 ? cc.q0[rec->cos]
+				: odp_amd_cls_queue_of(rec->cos, rec->queue);
 
 			fl |= MI_CLS_DLV_CLS;
 			d->dst_queue = (uint64_t)(uintptr_t)q;
-			if (grouped && mode_of_cos[r.cos] < 0) {
-				odp_pool_t vp = ODP_POOL_INVALID;
-				uint32_t vmax = 0;
-				int aggr = 0;
-				const int std = odp_amd_cls_cos_enq_mode(r.cos, &vp, &vmax, &aggr);
+			if (grouped && rx_cos_plain(mode_of_cos, rec->cos)) {
+				const int k = rx_qgroup_of(&g, q);
 
-				mode_of_cos[r.cos] = std > 0 && !aggr;
-			}
-			if (grouped && mode_of_cos[r.cos]) {
-				uint32_t sl = rx_qhash(q);
-
-				while (slot_grp[sl] && gq[slot_grp[sl] - 1] != q)
-					sl = (sl + 1) & (RX_GROUP_HASH - 1);
-				if (!slot_grp[sl]) {
-					if (ng == MI_CLS_DLV_GROUPS) {
-						grouped = 0;
-					} else {
-						gq[ng] = q;
-						slot_grp[sl] = (uint8_t)++ng;
-					}
-				}
-				if (grouped)
-					qid = (uint8_t)(slot_grp[sl] - 1);
+				if (k < 0)
+					grouped = 0;
+				else
+					qid = (uint8_t)k;
 			} else {
 				grouped = 0;
 			}
@@ -2204,11 +2272,6 @@ static int rx_dlv_start(rt_pktio_t *e, rx_set_t *s, rx_cnt_t *c)
 		d->qid = qid;
 		s->ent[ne++] = dst;
 	}
-#undef COS_SEEN
-	/* the pools' packets nobody took back */
-	for (int k = 0; k < npl; k++)
-		if (pl[k].used < pl[k].have)
-			odp_packet_free_multi(&got[pl[k].base + pl[k].used], pl[k].have - pl[k].used);
 	if (ne > MI_CLS_DLV_GROUP_MAX)   /* larger than the device grouping serves */
 		grouped = 0;
 	if (!grouped)   /* per-run enqueue (vectors, aggregators, > 64 queues) */
@@ -2217,8 +2280,8 @@ static int rx_dlv_start(rt_pktio_t *e, rx_set_t *s, rx_cnt_t *c)
 	s->ne = ne;
 	s->nold = nold;
 	s->grouped = grouped;
-	s->ng = ng;
-	memcpy(s->gq, gq, (size_t)ng * sizeof(odp_queue_t));
+	s->ng = g.n;
+	memcpy(s->gq, g.q, (size_t)g.n * sizeof(odp_queue_t));
 	s->cnt = *c;
 	s->dticket = 0;
 	s->delivering = 1;
@@ -2267,7 +2330,6 @@ static int rx_dlv_start(rt_pktio_t *e, rx_set_t *s, rx_cnt_t *c)
  * a receive call made wholly after the change. */
 static void rx_dlv_regen(rt_pktio_t *e, rx_set_t *s, rx_cnt_t *c)
 {
-	const odp_proto_layer_t layer = e->parse_layer;
 	uint32_t m = 0;
 	int rc = odp_amd_cls_classify_host(e->hdl, s->base, s->bytes, s->soff, s->slen, (uint32_t)s->n,
 					   s->res, 0);
@@ -2283,12 +2345,14 @@ static void rx_dlv_regen(rt_pktio_t *e, rx_set_t *s, rx_cnt_t *c)
 	}
 	for (uint32_t j = 0; j < s->ne; j++) {
 		odp_packet_t pkt = s->ent[j];
-		mi_cls_result_t r = s->res[s->dlv[j].rec];
+		mi_cls_result_t r;
+		odp_pool_t pool;
 		const uint32_t len = s->dlv[j].len;
+		const rx_verdict_t v = rx_decide(e, &s->res[s->dlv[j].rec], &r, &pool, NULL);
 
-		apply_layer(&r, layer);
-		if (r.outcome != MI_CLS_OUT_ENQ) {
-			if (r.outcome == MI_CLS_OUT_DISCARD || r.outcome == MI_CLS_OUT_LOOP)
+		if (v != RX_DELIVER) {
+			/* (its error flags were counted when the delivery started) */
+			if (v == RX_COS_DISCARD)
 				c->in_discards++;
 			if (!r.err) {
 				c->packets--;
@@ -2297,10 +2361,6 @@ static void rx_dlv_regen(rt_pktio_t *e, rx_set_t *s, rx_cnt_t *c)
 			odp_packet_free(pkt);
 			continue;
 		}
-		odp_pool_t pool = odp_amd_cls_pool_of(r.cos);
-
-		if (pool == ODP_POOL_INVALID)
-			pool = e->pool;
 		if (odp_packet_pool(pkt) != pool) {
 			/* _odp_pktio_packet_to_pool under the new CoS */
 			odp_packet_t np = odp_packet_alloc(pool, len);
@@ -2380,32 +2440,22 @@ static int rx_dlv_end(rt_pktio_t *e, rx_set_t *s, odp_packet_t out[], int max_ou
 		rx_dlv_regen(e, s, c);
 	const uint64_t tk1 = prof_ns();
 
-	if (!e->cls_enabled) {
-		for (uint32_t j = 0; j < s->ne; j++) {
-			if (num_rx < max_out)
-				out[num_rx++] = s->ent[j];
-			else
-				odp_packet_free(s->ent[j]);
-		}
-	} else if (s->grouped) {
-		rx_enqueue_groups(s, s->gq, s->ng, s->tmp);
-	} else if (s->ne) {
-		rx_enqueue(s->ent, (int)s->ne, s->tmp, (uint8_t *)(void *)(s->tmp + s->tmp_cap));
-	}
+	if (!e->cls_enabled)
+		num_rx = rx_to_caller(s->ent, (int)s->ne, out, max_out);
+	else if (s->grouped)
+		rx_enqueue_groups(s);
+	else if (s->ne)
+		rx_enqueue(s, s->ent, (int)s->ne);
 	s->ne = 0;
 	e->prof[9] += tk1 - tk0;
 	e->prof[10] += prof_ns() - tk1;
-	if (c->in_errors)
-		odp_atomic_add_u64(&e->in_errors, c->in_errors);
-	if (c->in_discards)
-		odp_atomic_add_u64(&e->in_discards, c->in_discards);
-	odp_atomic_add_u64(&e->in_octets, c->octets);
-	odp_atomic_add_u64(&e->in_packets, c->packets);
+	rx_cnt_flush(e, c);
 	return num_rx;
 }
 
-/* Delivery of set s on the host: rx_prepare, then the delivered packets,
- * compacted in arrival order, to their queues or out[]. */
+/* Delivery of set s on the host (the burst needs the host path): rx_prepare,
+ * then the delivered packets, compacted in arrival order, to their queues or
+ * out[]; the counters added.  t2: when the delivery began. */
 static int rx_deliver_host(rt_pktio_t *e, rx_set_t *s, rx_cnt_t *c, odp_packet_t out[], int max_out,
 			   uint64_t t2)
 {
@@ -2418,28 +2468,18 @@ static int rx_deliver_host(rt_pktio_t *e, rx_set_t *s, rx_cnt_t *c, odp_packet_t
 	for (int i = 0; i < s->n; i++)
 		if (s->pk[i] != ODP_PACKET_INVALID)
 			s->pk[nd++] = s->pk[i];
-	if (e->cls_enabled) {
-		if (s->tmp) {
-			rx_enqueue(s->pk, nd, s->tmp, (uint8_t *)(void *)(s->tmp + s->tmp_cap));
-		} else {
-			for (int i = 0; i < nd; i++)
-				cos_enq_run(&s->pk[i], 1);
-		}
-	} else {
-		for (int i = 0; i < nd; i++) {
-			if (num_rx < max_out)
-				out[num_rx++] = s->pk[i];
-			else
-				odp_packet_free(s->pk[i]);
-		}
-	}
-	e->prof[5] += prof_ns() - t3;
+	if (e->cls_enabled)
+		rx_enqueue(s, s->pk, nd);
+	else
+		num_rx = rx_to_caller(s->pk, nd, out, max_out);
+	const uint64_t t4 = prof_ns();
+
+	e->prof[5] += t4 - t3;
+	e->prof[2] += t4 - t2;
+	rx_cnt_flush(e, c);
 	return num_rx;
 }
 
-/* Wait for set s's records and deliver its packets: classified ones to their
- * CoS queues, the rest (classifier disabled) into out[] (at most max_out).
- * Returns the packets placed in out[]. */
 /* Wait for set s's classification; a burst that was in flight while the
  * control plane changed is classified again.  Returns 0, or -1 when the
  * burst was dropped (rx_drop). */
@@ -2473,30 +2513,8 @@ static int rx_classified(rt_pktio_t *e, rx_set_t *s)
 	}
 	e->prof[1] += prof_ns() - t1;
 	s->pending = 0;
-	if (!s->tmp || s->tmp_cap < s->n_cap) {
-		/* delivery scratch: packets (bulk allocation, then grouping by
-		 * queue), then one byte per frame (its pool, then its queue group) */
-		free(s->tmp);
-		s->tmp = malloc(s->n_cap * (sizeof(odp_packet_t) + 1u));
-		s->tmp_cap = s->tmp ? s->n_cap : 0;
-	}
+	rx_tmp_ensure(s);
 	return 0;
-}
-
-/* Deliver set s on the host (the burst needs the host path). */
-static int rx_finish_host(rt_pktio_t *e, rx_set_t *s, rx_cnt_t *c, odp_packet_t out[], int max_out,
-			  uint64_t t2)
-{
-	const int num_rx = rx_deliver_host(e, s, c, out, max_out, t2);
-
-	e->prof[2] += prof_ns() - t2;
-	if (c->in_errors)
-		odp_atomic_add_u64(&e->in_errors, c->in_errors);
-	if (c->in_discards)
-		odp_atomic_add_u64(&e->in_discards, c->in_discards);
-	odp_atomic_add_u64(&e->in_octets, c->octets);
-	odp_atomic_add_u64(&e->in_packets, c->packets);
-	return num_rx;
 }
 
 /* Wait for set s's records and deliver its packets now: classified ones to
@@ -2517,7 +2535,13 @@ static int rx_finish(rt_pktio_t *e, rx_set_t *s, odp_packet_t out[], int max_out
 		e->prof[2] += prof_ns() - t2;
 		return num_rx;
 	}
-	return rx_finish_host(e, s, &c, out, max_out, t2);
+	return rx_deliver_host(e, s, &c, out, max_out, t2);
+}
+
+/* Set of age k: staged k calls ago (age 0: this call). */
+static rx_set_t *rx_age(rt_pktio_t *e, int k)
+{
+	return &e->rs[(e->cur + RX_SETS - k) % RX_SETS];
 }
 
 /* Classifier on: wait for set s's records and start its GPU delivery,
@@ -2544,7 +2568,7 @@ static void rx_finish_start(rt_pktio_t *e, rx_set_t *s)
 		if (b->delivering)
 			(void)rx_dlv_end(e, b, NULL, 0);
 	}
-	(void)rx_finish_host(e, s, &c, NULL, 0, t2);
+	(void)rx_deliver_host(e, s, &c, NULL, 0, t2);
 }
 
 /* ------------------------------------------------------- receive chain
@@ -2561,12 +2585,7 @@ static int rx_chain_on(void)
 {
 	static int on = -1;
 
-	if (on < 0) {
-		const char *v = getenv("ODP_AMD_RX_CHAIN");
-
-		on = !(v && v[0] == '0');
-	}
-	return on;
+	return env_switch("ODP_AMD_RX_CHAIN", &on);
 }
 
 /* The chain's table for the current control-plane generation: refilled when
@@ -2617,8 +2636,6 @@ static int rxc_table(rt_pktio_t *e)
 	return e->rxtab_ok ? 0 : -1;
 }
 
-/* Submit set s's burst as a chain: 1, or 0 when it takes the other path
- * (nothing done then). */
 /* Whether this pktio's loop bursts can be staged by the GPU (the chain's
  * conditions, and an arena of page-locked pools to address them in). */
 static int rxc_loop_stage_ok(rt_pktio_t *e, rx_set_t *s, uint32_t max)
@@ -2635,8 +2652,10 @@ static int rxc_loop_stage_ok(rt_pktio_t *e, rx_set_t *s, uint32_t max)
 	       rxc_table(e) == 0;
 }
 
-/* A burst that does not take the chain: a loop burst left for the GPU to
- * stage is staged by the host now (the classic path reads its descriptors). */
+/* A burst that does not take the chain, or leaves it for the host path
+ * (rxc_end): a loop burst left for the GPU to stage is staged by the host now
+ * (the classic path reads its descriptors); one that cannot be is dropped
+ * and counted, s->n then 0.  Returns 0, rxc_submit's "not chained". */
 static int rxc_no(rt_pktio_t *e, rx_set_t *s)
 {
 	if (s->gstage) {
@@ -2676,6 +2695,8 @@ static int rxc_wait(rt_pktio_t *e, rx_set_t *s, int nj)
 	return rc;
 }
 
+/* Submit set s's burst as a chain: 1, or 0 when it takes the other path
+ * (nothing done then, but for rxc_no's staging). */
 static int rxc_submit(rt_pktio_t *e, rx_set_t *s)
 {
 	const uint32_t n = (uint32_t)s->n;
@@ -2859,15 +2880,11 @@ static int rxc_end(rt_pktio_t *e, rx_set_t *s, odp_packet_t out[], int max_out)
 			rx_drop(e, s, rc);
 			return 0;
 		}
-		if (s->gstage) {
-			s->gstage = 0;
-			if (loop_stage_hdrs(e, s, (uint32_t)s->n)) {
-				rx_drop(e, s, -ENOMEM);   /* freed and counted */
-				return 0;
-			}
-			if (rx_classify(e, s, 0))
-				return 0;   /* dropped and counted */
-		}
+		const int restage = s->gstage;
+
+		(void)rxc_no(e, s);
+		if (restage && (s->n == 0 || rx_classify(e, s, 0)))
+			return 0;   /* dropped and counted */
 		s->pending = 1;
 		return rx_finish(e, s, out, max_out);
 	}
@@ -2889,18 +2906,14 @@ static int rxc_end(rt_pktio_t *e, rx_set_t *s, odp_packet_t out[], int max_out)
 			if ((s->dec[i] & 3u) != MI_CLS_RXF_INPLACE)
 				odp_packet_free(s->pk[i]);
 	}
+	rx_tmp_ensure(s);
 	odp_packet_t *tmp = s->tmp;
+	uint8_t *cos = rx_tmp_bytes(s);
 
-	if (!tmp || s->tmp_cap < s->n_cap) {
-		free(s->tmp);
-		s->tmp = malloc(s->n_cap * (sizeof(odp_packet_t) + 1u));
-		s->tmp_cap = s->tmp ? s->n_cap : 0;
-		tmp = s->tmp;
-	}
 	if ((e->rxtab->flags & MI_CLS_RXT_GROUP) && tmp) {
 		/* per slice, in device order: group g holds frames perm[at ..
 		 * at + gcnt[g]) of the slice (indexes within it) of the queue whose
-		 * entries carry group g; queue stats per CoS of the queue */
+		 * entries carry group g */
 		for (int j = 0; j < s->nsl; j++) {
 			const uint32_t lo = s->sl_lo[j];
 			const uint32_t *gc = s->gcnt + (size_t)j * MI_CLS_DLV_GROUPS;
@@ -2912,48 +2925,25 @@ static int rxc_end(rt_pktio_t *e, rx_set_t *s, odp_packet_t out[], int max_out)
 
 				if (!num)
 					continue;
-				const uint32_t i0 = lo + pm[at];
-				const mi_cls_result_t *r0 = &s->res[i0];
+				const mi_cls_result_t *r0 = &s->res[lo + pm[at]];
 				const odp_queue_t q = (odp_queue_t)(uintptr_t)
 					e->rxtab->qh[e->rxtab->cos_q0[r0->cos] + r0->queue];
-				uint64_t ok[256], bad[256];
-				uint8_t seen[256], cl[256];
-				int ncos = 0;
+				const int one_cos = gc[g] >> 24;   /* the decide kernel saw one CoS in the group */
 
-				for (uint32_t k = 0; k < num; k++)
-					tmp[k] = (odp_packet_t)(uintptr_t)s->cent[lo + pm[at + k]];
-				int r = odp_queue_enq_multi(q, (const odp_event_t *)(void *)tmp, (int)num);
-
-				if (r < 0)
-					r = 0;
-				if ((uint32_t)r != num)
-					odp_packet_free_multi(&tmp[r], (int)num - r);
-				if (gc[g] >> 24) {
-					/* one CoS for the whole group (the decide kernel's) */
-					const uint32_t cos = (gc[g] >> 16) & 0xFFu;
-
-					odp_amd_cls_queue_stats_add(cos, cos_slot_of(cos, q), (uint64_t)r,
-								    (uint64_t)(num - (uint32_t)r));
-					at += num;
-					continue;
-				}
-				memset(seen, 0, sizeof(seen));
 				for (uint32_t k = 0; k < num; k++) {
-					const uint32_t cos = s->res[lo + pm[at + k]].cos;
-
-					if (!seen[cos]) {
-						seen[cos] = 1;
-						cl[ncos++] = (uint8_t)cos;
-						ok[cos] = 0;
-						bad[cos] = 0;
-					}
-					if (k < (uint32_t)r)
-						ok[cos]++;
-					else
-						bad[cos]++;
+					tmp[k] = (odp_packet_t)(uintptr_t)s->cent[lo + pm[at + k]];
+					if (!one_cos)
+						cos[k] = s->res[lo + pm[at + k]].cos;
 				}
-				for (int c = 0; c < ncos; c++)
-					odp_amd_cls_queue_stats_add(cl[c], cos_slot_of(cl[c], q), ok[cl[c]], bad[cl[c]]);
+				if (one_cos) {
+					const uint32_t c1 = (gc[g] >> 16) & 0xFFu;
+					const int r = rx_enq_plain(q, tmp, (int)num);
+
+					odp_amd_cls_queue_stats_add(c1, cos_slot_of(c1, q), (uint64_t)r,
+								    (uint64_t)((int)num - r));
+				} else {
+					rx_enq_group(q, tmp, cos, (int)num);
+				}
 				at += num;
 			}
 		}
@@ -2964,36 +2954,21 @@ static int rxc_end(rt_pktio_t *e, rx_set_t *s, odp_packet_t out[], int max_out)
 		for (int i = 0; i < s->n; i++)
 			if (s->cent[i])
 				s->pk[nd++] = (odp_packet_t)(uintptr_t)s->cent[i];
-		if (tmp)
-			rx_enqueue(s->pk, nd, tmp, (uint8_t *)(void *)(tmp + s->tmp_cap));
-		else
-			for (int i = 0; i < nd; i++)
-				cos_enq_run(&s->pk[i], 1);
+		rx_enqueue(s, s->pk, nd);
 	}
-	uint64_t errs = 0, disc = 0, octs = 0, pkts = 0;
+	rx_cnt_t c = { 0, 0, 0, 0 };
 
 	for (int j = 0; j < s->nsl; j++) {
-		errs += s->rxo[j].in_errors;
-		disc += s->rxo[j].in_discards;
-		octs += s->rxo[j].octets;
-		pkts += s->rxo[j].packets;
+		c.in_errors += s->rxo[j].in_errors;
+		c.in_discards += s->rxo[j].in_discards;
+		c.octets += s->rxo[j].octets;
+		c.packets += s->rxo[j].packets;
 	}
-	if (errs)
-		odp_atomic_add_u64(&e->in_errors, errs);
-	if (disc)
-		odp_atomic_add_u64(&e->in_discards, disc);
-	odp_atomic_add_u64(&e->in_octets, octs);
-	odp_atomic_add_u64(&e->in_packets, pkts);
+	rx_cnt_flush(e, &c);
 	e->prof[10] += prof_ns() - tk1;
 	(void)out;
 	(void)max_out;
 	return 0;
-}
-
-/* Set of age k: staged k calls ago (age 0: this call). */
-static rx_set_t *rx_age(rt_pktio_t *e, int k)
-{
-	return &e->rs[(e->cur + RX_SETS - k) % RX_SETS];
 }
 
 /* One receive call.  With the classifier enabled and more frames waiting at

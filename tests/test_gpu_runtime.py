@@ -94,18 +94,25 @@ def test_rx_loop_pktio(built, gpu, tmp_path):
     _run_case(tmp_path, zoo.prog_everything(), frames, pktio="loop")
 
 
+# the delivery paths of a burst: the receive chain (default), the GPU delivery
+# kernel without it, the host's, and the host's because no pool is page-locked
+DELIVERY_ENV = {"gpu": {}, "gpu_no_chain": {"ODP_AMD_RX_CHAIN": "0"},
+                "host": {"ODP_AMD_RX_GPU_DELIVER": "0"},
+                "pageable_pools": {"ODP_AMD_PINNED_POOLS": "0"}}
+
+
 @pytest.mark.parametrize("cos_pools", [0, 1])
-@pytest.mark.parametrize("delivery", ["gpu", "host", "pageable_pools"])
+@pytest.mark.parametrize("delivery", list(DELIVERY_ENV))
 def test_rx_delivery_paths(built, gpu, tmp_path, cos_pools, delivery):
-    """The receive delivery after classification on both paths: the GPU
-    delivery kernel (page-locked pools: metadata, frame copies and the
-    group-by-queue done by mi_cls_deliver_submit; loop packets classified in
-    place, copied only on a pool switch) and the host's
-    (ODP_AMD_RX_GPU_DELIVER=0, or pools in ordinary memory).  pcap and loop
-    pktios, shared pool (in place) and per-CoS pools (pool switch); every
-    queue's packets, metadata and counters as the reference's."""
-    env = {"gpu": {}, "host": {"ODP_AMD_RX_GPU_DELIVER": "0"},
-           "pageable_pools": {"ODP_AMD_PINNED_POOLS": "0"}}[delivery]
+    """The receive delivery after classification on every path: the receive
+    chain, the GPU delivery kernel without it (ODP_AMD_RX_CHAIN=0; page-locked
+    pools: metadata, frame copies and the group-by-queue done by
+    mi_cls_deliver_submit; loop packets classified in place, copied only on a
+    pool switch) and the host's (ODP_AMD_RX_GPU_DELIVER=0, or pools in
+    ordinary memory).  pcap and loop pktios, shared pool (in place) and
+    per-CoS pools (pool switch); every queue's packets, metadata and counters
+    as the reference's."""
+    env = DELIVERY_ENV[delivery]
     frames = H.pcap_frames([f for _, f in zoo.all_frames()])
     for pktio in ("pcap", "loop"):
         _run_case(tmp_path, zoo.prog_everything(), frames, mode="direct", pktio=pktio,
@@ -426,6 +433,39 @@ def test_rx_chain_small_pool(built, gpu, tmp_path):
     exp = H.expected(prog, frames, 1, 1, 4)[1]
     assert stats == exp, (stats, exp)   # in_packets, in_errors, in_discards (0), octets
     assert prof["chain_bursts"] >= 1, prof
+
+
+@pytest.mark.parametrize("delivery", list(DELIVERY_ENV))
+def test_rx_pool_runs_short(built, gpu, tmp_path, delivery):
+    """Every CoS pool (200 packets) is a third of its CoS's traffic and the
+    application frees nothing until the capture is through (direct mode drains
+    the queues afterwards): on every delivery path each queue receives exactly
+    the first 200 packets of its CoS in arrival order -- the frames a
+    frame-by-frame odp_packet_alloc would have served -- and every later
+    frame is counted in in_discards and leaves in_packets / in_octets
+    (pktio/loop.c:332-337, 352-355).  Bursts of 61 do not divide the pool."""
+    P = 200
+    env = DELIVERY_ENV[delivery]
+    prog, frames = _ports_prog(3)   # dflt, p0, p1, p2: one queue and one pool each
+    frames = frames[:12 * P]        # 3 P frames per CoS
+    pc = str(tmp_path / "in.pcap")
+    H.write_pcap(pc, frames)
+    rules = str(tmp_path / "rules.txt")
+    H.write_rules(rules, prog)
+    eq, (in_pk, in_err, in_disc, octets), eqs = H.expected(prog, frames, 1, 1, 4)
+    assert sorted(eq) == ["dflt", "p0", "p1", "p2"] and all(len(v) == 3 * P for v in eq.values())
+    for q, pkts in eq.items():
+        assert all(p[0] == q + "Pool" for p in pkts)   # a pool of its own, dflt too
+        for p in pkts[P:]:
+            in_disc += 1
+            if not p[2]:
+                in_pk -= 1
+                octets -= p[6]
+        eq[q] = pkts[:P]
+        eqs[(q, 0)] = [P, 0]
+    got = H.run_driver(f"pcap:in={pc}", rules, "direct", 4, 1, 1,
+                       env=dict(env, ODP_AMD_RX_BURST="61", RX_POOL_NUM=str(P)))
+    H.compare(got, (eq, (in_pk, in_err, in_disc, octets), eqs))
 
 
 def test_rx_loop_no_pipeline(built, gpu, tmp_path):
