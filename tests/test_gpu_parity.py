@@ -12,7 +12,7 @@ from odp_amd import pktgen as pg
 from odp_amd import rules as R
 from tests import refcases as RC
 from tests import zoo
-from tests.helpers import assert_same, gpu_run, oracle_run, summary
+from tests.helpers import assert_same, gpu_run, knobs, oracle_run, summary
 
 pytestmark = pytest.mark.gpu
 
@@ -23,6 +23,8 @@ ENGINE_ENV = {
     "nodiv": {"MI_CLS_DIV": "0"},      # no per-lane bit-vector rounds (CoS waterfall)
     "div": {"MI_CLS_DIV": "1"},        # per-lane bit-vector rounds even for flat programs
     "wpb4": {"MI_CLS_WPB": "4"},       # 4-wave blocks (own hot-region copy or HBM)
+    "wpb8": {"MI_CLS_WPB": "8"},       # one 8-wave block per CU (general kernels only)
+    "wpb12": {"MI_CLS_WPB": "12"},     # one 12-wave block per CU
     "wpb16": {"MI_CLS_WPB": "16"},     # one 16-wave block per CU sharing the LDS copy
     "nowide": {"MI_CLS_NO_WIDE": "1"},  # candidate lists instead of wide bitmap rows
     "nocand1": {"MI_CLS_NO_CAND1": "1"},   # no single-candidate engine (wide / lists)
@@ -38,18 +40,8 @@ def both(prog, batch, limits=(255, 8192, 4096), what="", engine="auto"):
     """engine "auto": bit-vector blocks where a CoS has <= 8 key classes,
     linear scan otherwise, per-lane rounds for CoS trees; the other engines
     force one of the kernel's paths (ENGINE_ENV)."""
-    import os
-    keys = ("MI_CLS_NO_BV", "MI_CLS_DIV", "MI_CLS_WPB", "MI_CLS_NO_WIDE", "MI_CLS_NO_CAND1",
-            "MI_CLS_NO_PORTMERGE", "MI_CLS_NO_FLAT", "MI_CLS_JIT", "MI_CLS_NO_JOINT")
-    old = {k: os.environ.pop(k, None) for k in keys}
-    os.environ.update(ENGINE_ENV[engine])
-    try:
+    with knobs(ENGINE_ENV[engine]):
         got = gpu_run(prog, batch, limits, spec=engine == "spec")
-    finally:
-        for k in keys:
-            os.environ.pop(k, None)
-            if old[k] is not None:
-                os.environ[k] = old[k]
     exp, _ = oracle_run(prog, batch, limits)
     assert_same(got, exp, batch, f"{what} [{engine}]")
     return got
@@ -103,8 +95,8 @@ def test_zoo_no_default(built, gpu):
     assert s["discard"] > 0 and s["cos_drop"] > 0
 
 
-@pytest.mark.parametrize("engine", ["auto", "linear", "nodiv", "div", "wpb16", "nowide", "nocand1",
-                                    "noportmerge", "noflat", "spec", "nojit", "nojoint"])
+@pytest.mark.parametrize("engine", ["auto", "linear", "nodiv", "div", "wpb8", "wpb12", "wpb16", "nowide",
+                                    "nocand1", "noportmerge", "noflat", "spec", "nojit", "nojoint"])
 @pytest.mark.parametrize("seed", range(12))
 def test_random_programs_fuzz(built, gpu, seed, engine):
     rng = np.random.default_rng(1000 + seed)
@@ -117,8 +109,8 @@ def test_random_programs_fuzz(built, gpu, seed, engine):
     both(prog, b, what=f"fuzz seed {seed}", engine=engine)
 
 
-@pytest.mark.parametrize("engine", ["auto", "linear", "nodiv", "wpb4", "wpb16", "nowide", "nocand1",
-                                    "noportmerge", "noflat", "spec", "nojit", "nojoint"])
+@pytest.mark.parametrize("engine", ["auto", "linear", "nodiv", "wpb4", "wpb8", "wpb12", "wpb16", "nowide",
+                                    "nocand1", "noportmerge", "noflat", "spec", "nojit", "nojoint"])
 @pytest.mark.parametrize("cfg,n", [(1, 10_000), (2, 100_000), (3, 50_000), (4, 50_000),
                                    (5, 20_000)])
 def test_configs_small(built, gpu, cfg, n, engine):
@@ -185,7 +177,8 @@ def _joint_tree(rng, n, leaf_kind):
     return b, prog
 
 
-@pytest.mark.parametrize("engine", ["auto", "nojoint", "wpb4", "linear", "spec", "nojit"])
+@pytest.mark.parametrize("engine", ["auto", "nojoint", "wpb4", "wpb8", "wpb12", "linear", "spec",
+                                    "nojit"])
 @pytest.mark.parametrize("leaf_kind", ["dport", "dip", "sip6"])
 def test_joint_direct_tree_levels(built, gpu, leaf_kind, engine):
     """A tree level whose CoS all key on one class is one joint direct group
@@ -258,7 +251,8 @@ def _joint_bitmap_tree(rng, n, pair):
     return b, prog
 
 
-@pytest.mark.parametrize("engine", ["auto", "nojoint", "wpb4", "linear", "spec", "nojit"])
+@pytest.mark.parametrize("engine", ["auto", "nojoint", "wpb4", "wpb8", "wpb12", "linear", "spec",
+                                    "nojit"])
 @pytest.mark.parametrize("pair", ["dport", "sip6"])
 def test_joint_bitmap_tree_levels(built, gpu, pair, engine):
     """A tree level whose CoS have bitmap blocks over the same two classes
@@ -573,7 +567,7 @@ def _far_l4_errors(n, stats):
 
 
 @pytest.mark.parametrize("stats", [False, True], ids=["nostats", "stats"])
-@pytest.mark.parametrize("engine", ["spec", "nojit", "wpb4", "nojoint"])
+@pytest.mark.parametrize("engine", ["spec", "nojit", "wpb4", "wpb8", "wpb12", "nojoint"])
 def test_far_l4_checks_deferred(built, gpu, engine, stats):
     """Tree kernels stage bytes 64.. per lane after the parse and check the L4
     headers whose bytes lie there once they land (the first descent round
