@@ -17,6 +17,11 @@
                          compiled UNCHANGED against these headers and libraries
                          by oracle/Makefile (only where the reference tree is
                          present; the binary travels, it is never committed)
+  oracle/_ref/libodp_ref.so, oracle/_ref/ref_shim_main
+                         test infrastructure: the reference's parser, checksum
+                         and classifier sources, compiled UNCHANGED, with
+                         oracle/ref_shim.c, as a library (oracle/reflib.py) and
+                         as a sanitised stand-alone program; same rule
 """
 from __future__ import annotations
 
@@ -127,7 +132,7 @@ def build(force: bool = False, out_dir: str = PKG, defines=(), src_dir: str = SR
               "-lpthread"])
         built.append(odph_so)
     if out_dir == PKG:
-        for b in (build_example(force), build_test_drivers(force)):
+        for b in (build_example(force), build_reflib(force), build_test_drivers(force)):
             if b:
                 built.append(b)
     return built
@@ -191,6 +196,38 @@ def build_example(force: bool = False):
          (["-B"] if force else []))
     after = os.path.getmtime(EXAMPLE) if os.path.exists(EXAMPLE) else None
     return EXAMPLE if after != before else None
+
+
+REFLIB = os.path.join(ROOT, "oracle", "_ref", "libodp_ref.so")
+REF_SHIM_MAIN = os.path.join(ROOT, "oracle", "_ref", "ref_shim_main")
+
+
+def build_reflib(force: bool = False):
+    """Compile the reference's parser, checksum and classifier sources,
+    unchanged, with oracle/ref_shim.c into oracle/_ref/libodp_ref.so (the
+    library oracle/reflib.py binds; recipe: oracle/Makefile ref-lib), and the
+    same sources as the stand-alone, sanitised oracle/_ref/ref_shim_main
+    (ref-shim-main; left out where the compiler has no static sanitiser
+    runtimes).  Test infrastructure, never committed; nothing is built where
+    the reference tree is absent: what was built where it is present travels.
+    The recipe and the shim come with oracle/: an oracle/ directory from
+    before them (an older checker beside this build) builds nothing either,
+    and oracle/reflib.py, which is then absent too, is what names build()."""
+    oracle_dir = os.path.join(ROOT, "oracle")
+    with open(os.path.join(oracle_dir, "Makefile")) as f:
+        has_recipe = any(ln.startswith("ref-lib") for ln in f)
+    if not has_recipe or not os.path.exists(os.path.join(oracle_dir, "ref_shim.c")):
+        return None
+    before = os.path.getmtime(REFLIB) if os.path.exists(REFLIB) else None
+    mk = ["make", "-s", "-C", oracle_dir]
+    _run(mk + ["ref-lib"] + (["-B"] if force else []))
+    try:
+        _run(mk + ["ref-shim-main"])
+    except RuntimeError as e:
+        if "cannot find" not in str(e):
+            raise
+    after = os.path.getmtime(REFLIB) if os.path.exists(REFLIB) else None
+    return REFLIB if after != before else None
 
 
 if __name__ == "__main__":

@@ -1266,8 +1266,11 @@ FLAG(icmp, 25)
 
 int odp_packet_has_error(odp_packet_t pkt) { return rt_pkt_hdr(pkt)->err != 0; }
 int odp_packet_has_l2_error(odp_packet_t pkt) { return (rt_pkt_hdr(pkt)->err & 0x01) != 0; }
-int odp_packet_has_l3_error(odp_packet_t pkt) { return (rt_pkt_hdr(pkt)->err & 0x06) != 0; }
-int odp_packet_has_l4_error(odp_packet_t pkt) { return (rt_pkt_hdr(pkt)->err & 0x78) != 0; }
+/* packet_flag_inlines.h:266-293: L2 = snap_len_err, L3 = ip_err alone, L4 =
+ * tcp_err | udp_err (an SCTP error or a bare l4_chksum_err, e.g. a zero UDP
+ * checksum over IPv6, shows in has_error and the checksum status only) */
+int odp_packet_has_l3_error(odp_packet_t pkt) { return (rt_pkt_hdr(pkt)->err & 0x02) != 0; }
+int odp_packet_has_l4_error(odp_packet_t pkt) { return (rt_pkt_hdr(pkt)->err & 0x18) != 0; }
 
 /* packet_inlines.h:389-420: input_flags l3/l4_chksum_done (bits 30/31),
  * error bits l3_chksum_err (2) / l4_chksum_err (6) */

@@ -7,14 +7,19 @@
  *   load this library, and only as the checker / the timed CPU baseline.  The
  *   product path (odp_amd/, libodp_cls.so, libmi_cls.so) never links it.
  *
- * Parity status: PINNED by the reference's own fixtures (see DESIGN.md
- * "Oracle"): udp64.pcap + the example's rule (pktio_env:21-23), the parser
- * frames of test/common/test_packet_*.h with the flag assertions of
- * test/validation/api/packet/packet.c:3745-4560, the per-term MATCH/NO_MATCH
- * cases of odp_classification_test_pmr.c, and the input_flags words the
- * survey observed from the reference build.
- * The reference itself cannot be built here (it needs configure-generated
- * autoheaders and ~20 library stand-ins), so it is not linked.
+ * Parity status: PINNED by the reference's own compiled code (see DESIGN.md
+ * "Oracle"): oracle/Makefile's ref-lib target compiles the reference's
+ * odp_parse.c, odp_packet.c, odp_chksum.c, odp_hash_crc_gen.c,
+ * odp_classification.c and arch/default/odp_hash_crc32.c unchanged, with
+ * ref_shim.c, into _ref/libodp_ref.so, and tests/test_oracle_vs_reference.py
+ * compares this restatement with it record for record at the reference's
+ * limits (64 / 256 / 8): the zoo, swept header fields, fuzzed programs with
+ * deletes over mutated and truncated frames, every pktin option row, and
+ * odp_packet_parse through tests/parse_model.py.  Pinned by fixtures only
+ * (udp64.pcap, the parser frames and flag assertions of packet.c:3745-4560,
+ * the MATCH/NO_MATCH cases of odp_classification_test_pmr.c, SURVEY.md
+ * Appendix A): CoS cycles (the reference never returns), table limits above
+ * the stock ones, and LSO.  This library never links the reference.
  *
  * Everything below is a plain scalar restatement, written from the behaviour
  * of the reference (file:line citations are relative to

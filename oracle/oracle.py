@@ -4,7 +4,8 @@
 bench.py's cpu_baseline leg may import this module: it is the checker the
 HIP path is compared against, never part of the product path.
 
-Parity: pinned by the reference's own fixtures -- see
+Parity: pinned by the reference's own compiled code (oracle/reflib.py,
+tests/test_oracle_vs_reference.py) and fixtures -- see
 oracle/odp_cls_oracle.c's header and DESIGN.md ("Oracle").
 """
 from __future__ import annotations

@@ -101,10 +101,10 @@ def result_word(flags, err):
             bit = err != 0
         elif name == "has_l2_error":
             bit = err & 0x01
-        elif name == "has_l3_error":
-            bit = err & 0x06
-        elif name == "has_l4_error":
-            bit = err & 0x78
+        elif name == "has_l3_error":      # ip_err alone (packet_flag_inlines.h:277-284)
+            bit = err & 0x02
+        elif name == "has_l4_error":      # tcp_err | udp_err (packet_flag_inlines.h:286-293)
+            bit = err & 0x18
         else:
             bit = (flags >> FLAG_BITS[name]) & 1
         w |= (1 if bit else 0) << i
