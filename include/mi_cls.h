@@ -359,6 +359,12 @@ typedef struct mi_cls_tx_desc {
 #define MI_CLS_TXF_L3     0x02u  /* l3_chksum: insert (1) / do not insert (0)     */
 #define MI_CLS_TXF_L4_SET 0x04u  /* l4_chksum_set                                 */
 #define MI_CLS_TXF_L4     0x08u  /* l4_chksum                                     */
+/* the packet's metadata flags (odp_packet_has_udp() ...), read by mi_cls_tx_hash
+ * only: the checksum entries ignore them */
+#define MI_CLS_TXF_UDP    0x10u
+#define MI_CLS_TXF_TCP    0x20u
+#define MI_CLS_TXF_IPV4   0x40u
+#define MI_CLS_TXF_IPV6   0x80u
 
 /* done[i]: the checksums written into packet i */
 #define MI_CLS_TX_IPV4 1u
@@ -393,6 +399,52 @@ int mi_cls_chksum_insert_host_submit(mi_cls_ctx_t *ctx, uint8_t *pkts_host, size
 				     const mi_cls_tx_desc_t *desc_host, uint32_t n, uint64_t pktout_opt,
 				     uint8_t *done_host, uint64_t *ticket);
 int mi_cls_chksum_insert_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
+
+/* ------------------------------------------------------------------------
+ * The pktin flow hash of the loop pktio (reference pktio/loop.c:479-530
+ * get_dest_queue), a step of the transmit kernel: per packet
+ * odp_hash_crc32c(string, n, 0) -- the raw reflected CRC-32C, no final
+ * inversion -- into hash_out[i]; the modulo by the queue count is the
+ * caller's.  The string is decided by the packet's metadata alone, the
+ * MI_CLS_TXF_UDP / TCP / IPV4 / IPV6 bits of its descriptor and l3 / l4 (the
+ * frame is not parsed), under hash_proto = odp_pktin_hash_proto_t.all_bits
+ * (bit 0 ipv4_udp, 1 ipv4_tcp, 2 ipv4, 3 ipv6_udp, 4 ipv6_tcp, 5 ipv6;
+ * 1..63):
+ *   l4 valid: (ipv4_udp | ipv6_udp) and TXF_UDP: the 4 bytes at l4 when
+ *   l4 + 8 <= len; else (ipv4_tcp | ipv6_tcp) and TXF_TCP: the 4 bytes at l4
+ *   when l4 + 20 <= len.  A UDP packet whose header does not fit appends
+ *   nothing (the TCP branch is not tried).
+ *   l3 valid: ipv4 and TXF_IPV4: the 8 bytes at l3 + 12 when l3 + 20 <= len;
+ *   else ipv6 and TXF_IPV6: the 32 bytes at l3 + 8 when l3 + 40 <= len.
+ *   The empty string hashes to 0.
+ * chksum != 0: the same launch also inserts the checksums, exactly as
+ * mi_cls_chksum_insert with this pktout_opt, these descriptors and `done`,
+ * and the hash is of the frame as the insertion leaves it (the reference
+ * fixes the checksums, then picks the queue: loop.c:581-582).  That matters
+ * only where the metadata contradicts the bytes and puts a checksum field
+ * into the string: TXF_IPV6 on an IPv4 frame, an l4 inside the IPv4 header.
+ * chksum == 0 (no default and no override of the call asks for a checksum):
+ * the hash alone; no frame byte is written, pktout_opt is not read and done,
+ * where given, is zeroed.  hash_out: n words, required.  Otherwise the
+ * arguments, the batch contract, the host forms (in place when every array,
+ * hash_out too, is page-locked; else staged, hash_out copied back with done
+ * and -- chksum != 0 only -- the frames), the tickets and the error codes
+ * are those of mi_cls_chksum_insert*.
+ * ---------------------------------------------------------------------- */
+int mi_cls_tx_hash(mi_cls_ctx_t *ctx, uint8_t *pkts_dev, const uint32_t *off_dev,
+		   const uint16_t *len_dev, const mi_cls_tx_desc_t *desc_dev, uint32_t n,
+		   uint64_t pktout_opt, uint8_t *done_dev, uint32_t hash_proto, uint32_t *hash_out_dev,
+		   int chksum, void *stream);
+int mi_cls_tx_hash_host(mi_cls_ctx_t *ctx, uint8_t *pkts_host, size_t bytes,
+			const uint32_t *off_host, const uint16_t *len_host,
+			const mi_cls_tx_desc_t *desc_host, uint32_t n, uint64_t pktout_opt,
+			uint8_t *done_host, uint32_t hash_proto, uint32_t *hash_out_host, int chksum);
+int mi_cls_tx_hash_host_submit(mi_cls_ctx_t *ctx, uint8_t *pkts_host, size_t bytes,
+			       const uint32_t *off_host, const uint16_t *len_host,
+			       const mi_cls_tx_desc_t *desc_host, uint32_t n, uint64_t pktout_opt,
+			       uint8_t *done_host, uint32_t hash_proto, uint32_t *hash_out_host,
+			       int chksum, uint64_t *ticket);
+int mi_cls_tx_hash_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
 
 /* ------------------------------------------------------------------------
  * The parse on its own: odp_packet_parse() / odp_packet_parse_multi() for a

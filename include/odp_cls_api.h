@@ -327,6 +327,13 @@ int odp_amd_cls_chksum_insert_host(odp_pktio_t pktio, uint8_t *pkts, size_t byte
 				   const uint32_t *off, const uint16_t *len,
 				   const struct mi_cls_tx_desc *desc, uint32_t n, uint64_t pktout_opt,
 				   uint8_t *done);
+/* The send burst's launch with the pktin flow hash of every packet
+ * (mi_cls_tx_hash_host: hash_proto the pktio's odp_pktin_hash_proto_t bits,
+ * hash_out n words; chksum 0: the hash alone, no frame byte written). */
+int odp_amd_cls_tx_hash_host(odp_pktio_t pktio, uint8_t *pkts, size_t bytes, const uint32_t *off,
+			     const uint16_t *len, const struct mi_cls_tx_desc *desc, uint32_t n,
+			     uint64_t pktout_opt, uint8_t *done, uint32_t hash_proto, uint32_t *hash_out,
+			     int chksum);
 
 /* LSO segmentation of a send call on the pktio's transmit context, the one
  * odp_amd_cls_chksum_insert_host uses (mi_cls_lso_segment_host: sources and

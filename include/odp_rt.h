@@ -522,6 +522,17 @@ int odp_packet_has_tcp(odp_packet_t pkt);
 int odp_packet_has_sctp(odp_packet_t pkt);
 int odp_packet_has_icmp(odp_packet_t pkt);
 int odp_packet_has_flow_hash(odp_packet_t pkt);
+/* odp_packet_flags.c: a loop pktio's pktin hash reads these four and the
+ * l3 / l4 offsets, not the frame */
+void odp_packet_has_ipv4_set(odp_packet_t pkt, int val);
+void odp_packet_has_ipv6_set(odp_packet_t pkt, int val);
+void odp_packet_has_udp_set(odp_packet_t pkt, int val);
+void odp_packet_has_tcp_set(odp_packet_t pkt, int val);
+/* include/odp/api/spec/hash.h: CRC-32C (Castagnoli) from init_val, no final
+ * inversion (host code).  What a loop pktio with several hashed input queues
+ * computes, on the GPU, over a sent packet's ports and addresses: the packet
+ * arrives on input queue odp_hash_crc32c(string, n, 0) % num_queues. */
+uint32_t odp_hash_crc32c(const void *data, uint32_t data_len, uint32_t init_val);
 int odp_packet_has_ts(odp_packet_t pkt);
 
 /* Parsing a packet the application holds (include/odp/api/spec/packet.h,
@@ -1023,6 +1034,67 @@ typedef union odp_pktio_set_op_t {
 	uint32_t all_bits;
 } odp_pktio_set_op_t;
 
+/* packet_io_stats.h: the counters a pktio and its queues keep */
+typedef struct odp_pktio_stats_capability_t {
+	struct {
+		union {
+			struct {
+				uint64_t in_octets : 1;
+				uint64_t in_packets : 1;
+				uint64_t in_ucast_pkts : 1;
+				uint64_t in_mcast_pkts : 1;
+				uint64_t in_bcast_pkts : 1;
+				uint64_t in_discards : 1;
+				uint64_t in_errors : 1;
+				uint64_t out_octets : 1;
+				uint64_t out_packets : 1;
+				uint64_t out_ucast_pkts : 1;
+				uint64_t out_mcast_pkts : 1;
+				uint64_t out_bcast_pkts : 1;
+				uint64_t out_discards : 1;
+				uint64_t out_errors : 1;
+			} counter;
+			uint64_t all_counters;
+		};
+	} pktio;
+	struct {
+		union {
+			struct {
+				uint64_t octets : 1;
+				uint64_t packets : 1;
+				uint64_t discards : 1;
+				uint64_t errors : 1;
+			} counter;
+			uint64_t all_counters;
+		};
+	} pktin_queue;
+	struct {
+		union {
+			struct {
+				uint64_t octets : 1;
+				uint64_t packets : 1;
+				uint64_t discards : 1;
+				uint64_t errors : 1;
+			} counter;
+			uint64_t all_counters;
+		};
+	} pktout_queue;
+} odp_pktio_stats_capability_t;
+
+typedef struct odp_pktin_queue_stats_t {
+	uint64_t octets;
+	uint64_t packets;
+	uint64_t discards;
+	uint64_t errors;
+} odp_pktin_queue_stats_t;
+
+typedef struct odp_pktout_queue_stats_t {
+	uint64_t octets;
+	uint64_t packets;
+	uint64_t discards;
+	uint64_t errors;
+} odp_pktout_queue_stats_t;
+
 typedef struct odp_pktio_capability_t {
 	uint32_t max_input_queues;
 	uint32_t min_input_queue_size;
@@ -1042,6 +1114,7 @@ typedef struct odp_pktio_capability_t {
 	odp_support_t loop_supported;
 	odp_bool_t vector_supported;
 	odp_lso_capability_t lso;
+	odp_pktio_stats_capability_t stats;
 } odp_pktio_capability_t;
 
 typedef struct odp_pktio_stats_t {
@@ -1112,6 +1185,10 @@ int odp_pktio_mac_addr(odp_pktio_t pktio, void *mac_addr, int size);
 uint32_t odp_pktio_mtu(odp_pktio_t pktio);
 int odp_pktio_stats(odp_pktio_t pktio, odp_pktio_stats_t *stats);
 int odp_pktio_stats_reset(odp_pktio_t pktio);
+/* per-queue counters (loop.c:781-805); odp_pktio_stats is their sum */
+int odp_pktin_queue_stats(odp_pktin_queue_t queue, odp_pktin_queue_stats_t *stats);
+int odp_pktin_event_queue_stats(odp_pktio_t pktio, odp_queue_t queue, odp_pktin_queue_stats_t *stats);
+int odp_pktout_queue_stats(odp_pktout_queue_t queue, odp_pktout_queue_stats_t *stats);
 int odp_pktio_info(odp_pktio_t pktio, odp_pktio_info_t *info);
 int odp_pktio_index(odp_pktio_t pktio);
 void odp_pktio_print(odp_pktio_t pktio);
@@ -1125,6 +1202,10 @@ int odp_amd_pktio_rx_idle(odp_pktio_t pktio);
  * and how many of them went through the bounce buffer (a packet outside the
  * page-locked pools); 0, or -1 on a bad handle. */
 int odp_amd_pktio_tx_stats(odp_pktio_t pktio, uint64_t *bursts, uint64_t *bounced);
+/* Of those calls, the ones whose launch also computed the pktin flow hash (a
+ * loop pktio with several hashed input queues: one launch per send call
+ * either way); 0, or -1 on a bad handle. */
+int odp_amd_pktio_txq_stats(odp_pktio_t pktio, uint64_t *hashed);
 /* odp_pktout_send_lso calls of the pktio that ran the LSO kernel, and how many
  * of them went through the bounce buffer; 0, or -1 on a bad handle. */
 int odp_amd_pktio_lso_stats(odp_pktio_t pktio, uint64_t *bursts, uint64_t *bounced);

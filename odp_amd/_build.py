@@ -67,7 +67,7 @@ def build(force: bool = False, out_dir: str = PKG, defines=(), src_dir: str = SR
     odph_so = os.path.join(out_dir, "libodph.so")
     rt_hdrs = hdrs + [os.path.join(INC, "odp_rt.h"), os.path.join(INC, "odp_api.h"),
                       os.path.join(INC, "odp", "helper", "odph_api.h"),
-                      os.path.join(SRC, "odp_rt_internal.h")]
+                      os.path.join(SRC, "odp_rt_internal.h"), os.path.join(SRC, "odp_txq.h")]
     built = []
     mi_hdr = os.path.join(SRC, "mi_cls_dev.h")
     prog_hdr = os.path.join(SRC, "mi_cls_prog.h")
@@ -77,7 +77,7 @@ def build(force: bool = False, out_dir: str = PKG, defines=(), src_dir: str = SR
     host_deps = [asm_src, spec_src, prog_hdr, os.path.join(SRC, "mi_cls_asm.h"),
                  os.path.join(SRC, "mi_cls_spec.h")]
     k_srcs = [os.path.join(SRC, f"mi_cls_k{w}.hip") for w in (4, 8, 12, 16, "f", "f12", "f16", "c4",
-                                                              "c16", "d", "t", "p", "l")]
+                                                              "c16", "d", "t", "h", "p", "l")]
     tx_hdr = os.path.join(SRC, "mi_cls_tx_dev.h")
     parse_hdr = os.path.join(SRC, "mi_cls_parse_dev.h")
     lso_hdr = os.path.join(SRC, "mi_cls_lso_dev.h")
@@ -166,7 +166,7 @@ def build_test_drivers(force: bool = False):
     built = None
     deps = [os.path.join(PKG, "libodp_cls.so"), os.path.join(PKG, "libodph.so"),
             os.path.join(INC, "odp_rt.h"), os.path.join(INC, "odp", "helper", "odph_api.h")]
-    for name in ("rx_driver", "rt_unit", "tx_driver", "parse_driver", "lso_driver"):
+    for name in ("rx_driver", "rt_unit", "tx_driver", "parse_driver", "lso_driver", "mq_driver"):
         src = os.path.join(ROOT, "tests", "rt", name + ".c")
         if not os.path.exists(src):
             continue

@@ -169,6 +169,11 @@ def _load():
         "mi_cls_chksum_insert_host_submit": (i32, [vp, vp, C.c_size_t, vp, vp, vp, u32, C.c_uint64, vp,
                                                    C.POINTER(C.c_uint64)]),
         "mi_cls_chksum_insert_host_wait": (i32, [vp, C.c_uint64]),
+        "mi_cls_tx_hash": (i32, [vp, vp, vp, vp, vp, u32, C.c_uint64, vp, u32, vp, i32, vp]),
+        "mi_cls_tx_hash_host": (i32, [vp, vp, C.c_size_t, vp, vp, vp, u32, C.c_uint64, vp, u32, vp, i32]),
+        "mi_cls_tx_hash_host_submit": (i32, [vp, vp, C.c_size_t, vp, vp, vp, u32, C.c_uint64, vp, u32, vp, i32,
+                                             C.POINTER(C.c_uint64)]),
+        "mi_cls_tx_hash_host_wait": (i32, [vp, C.c_uint64]),
         "mi_cls_parse": (i32, [vp, vp, vp, vp, u32, C.POINTER(ParseParam), vp, vp]),
         "mi_cls_parse_host": (i32, [vp, vp, C.c_size_t, vp, vp, u32, C.POINTER(ParseParam), vp]),
         "mi_cls_parse_host_submit": (i32, [vp, vp, C.c_size_t, vp, vp, u32, C.POINTER(ParseParam), vp,
@@ -245,7 +250,8 @@ def _h(x):
 
 
 # mi_cls_tx_desc_t (include/mi_cls.h): l3, l4, flags (bit 0 l3_chksum_set,
-# 1 l3_chksum, 2 l4_chksum_set, 3 l4_chksum)
+# 1 l3_chksum, 2 l4_chksum_set, 3 l4_chksum; for mi_cls_tx_hash bits 4-7: the
+# packet has UDP / TCP / IPv4 / IPv6)
 TX_DESC_DTYPE = np.dtype([("l3", "<u2"), ("l4", "<u2"), ("flags", "u1"), ("rsv", "u1", (3,))])
 
 
@@ -319,6 +325,60 @@ class TxContext(_FeatureContext):
             rc = self.L.mi_cls_chksum_insert_host(*args)
         if rc != 0:
             raise RuntimeError(f"mi_cls_chksum_insert_host: {rc}")
+
+
+    def hash_device(self, d_buf, d_off, d_len, d_desc, n, opt, d_done, hash_proto, d_hash, chksum, stream=0):
+        """mi_cls_tx_hash on device pointers (ints), stream-ordered.  Returns
+        the C status."""
+        return self.L.mi_cls_tx_hash(self.ctx, d_buf, d_off, d_len, d_desc, n, int(opt), d_done or None,
+                                     int(hash_proto), d_hash, int(bool(chksum)), stream or None)
+
+    def hash(self, batch, desc, hash_proto, opt=0, chksum=False, device="cuda:0", poison=0xA5A5A5A5):
+        """mi_cls_tx_hash: the pktin flow hash of every packet (pktio/loop.c
+        get_dest_queue before its modulo) under hash_proto
+        (odp_pktin_hash_proto_t.all_bits), from the descriptors' flag bits
+        4-7 and offsets; chksum: the same launch also inserts the checksums
+        as insert() does.  The hash words hold `poison` before the launch.
+        Returns (buffer bytes, done bytes, hash words)."""
+        import torch
+        dev = torch.device(device)
+        n = batch.n
+        desc = np.ascontiguousarray(desc, dtype=TX_DESC_DTYPE)
+        assert desc.shape[0] == n
+        t_buf = torch.from_numpy(np.ascontiguousarray(batch.buf)).to(dev)
+        t_off = torch.from_numpy(batch.off.astype(np.uint32).view(np.int32)).to(dev)
+        t_len = torch.from_numpy(batch.len.astype(np.uint16).view(np.int16)).to(dev)
+        t_desc = torch.from_numpy(desc.view(np.int64).copy() if n else np.zeros(1, np.int64)).to(dev)
+        t_done = torch.full((max(1, n),), 0xEE, dtype=torch.uint8, device=dev)
+        t_hash = torch.from_numpy(np.full(max(1, n) + 1, poison, np.uint32).view(np.int32)).to(dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.hash_device(t_buf.data_ptr(), t_off.data_ptr(), t_len.data_ptr(), t_desc.data_ptr(), n,
+                              opt, t_done.data_ptr(), hash_proto, t_hash.data_ptr(), chksum, stream)
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_tx_hash: {rc} ({self.L.mi_cls_strerror(rc).decode()})")
+        torch.cuda.synchronize(dev)
+        h = t_hash.cpu().numpy().view(np.uint32)
+        if h[n] != poison:
+            raise RuntimeError("mi_cls_tx_hash wrote past its n hash words")
+        return t_buf.cpu().numpy(), t_done.cpu().numpy()[:n], h[:n].copy()
+
+    def hash_host(self, buf, off, ln, desc, hash_proto, hash_out, opt=0, chksum=False, done=None,
+                  submit=False):
+        """mi_cls_tx_hash_host on numpy arrays, as insert_host; hash_out
+        (uint32, n words) receives the hashes."""
+        n = int(off.shape[0])
+        args = (self.ctx, buf.ctypes.data, buf.nbytes, off.ctypes.data, ln.ctypes.data,
+                desc.ctypes.data, n, int(opt), done.ctypes.data if done is not None else None,
+                int(hash_proto), hash_out.ctypes.data, int(bool(chksum)))
+        if submit:
+            t = C.c_uint64()
+            rc = self.L.mi_cls_tx_hash_host_submit(*args, C.byref(t))
+            if rc == 0:
+                rc = self.L.mi_cls_tx_hash_host_wait(self.ctx, t.value)
+        else:
+            rc = self.L.mi_cls_tx_hash_host(*args)
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_tx_hash_host: {rc}")
 
 
 def chksum_insert(batch, desc, opt, gpu: int = 0):

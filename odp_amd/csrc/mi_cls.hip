@@ -138,6 +138,8 @@ static int preload_kernels(int device)
 	chk(mi_cls_launch_rx_chain(nullptr, ra, mi_cls_rxdev_t{}, true));
 	chk(mi_cls_launch_rx_stage(nullptr, ra, mi_cls_rxdev_t{}, 0, true));
 	chk(mi_cls_launch_tx(0, nullptr, TxArgs{}));
+	chk(mi_cls_launch_tx_hash(true, 0, nullptr, TxHashArgs{}));
+	chk(mi_cls_launch_tx_hash(false, 0, nullptr, TxHashArgs{}));
 	for (uint32_t proto : { MI_CLS_PROTO_ETH, MI_CLS_PROTO_IPV4, MI_CLS_PROTO_IPV6 })
 		for (int ck = 0; ck < 2; ++ck)
 			chk(mi_cls_launch_parse(proto, ck != 0, 0, nullptr, ParseArgs{}));
@@ -763,6 +765,10 @@ static int stage_up(mi_cls_ctx_t *c, const uint8_t *frames, size_t bytes, size_t
 // (the same bytes when src == dst).
 static mi_cls_tx_desc_t *stg_tx_desc(const mi_cls_ctx_t *c) { return (mi_cls_tx_desc_t *)c->d_out; }
 static uint8_t *stg_tx_done(const mi_cls_ctx_t *c) { return (uint8_t *)(stg_tx_desc(c) + c->n_cap); }
+// the flow hash (mi_cls_tx_hash_host), n entries: d_out = n_cap descriptors,
+// then n_cap hash words, then the done bytes
+static uint32_t *stg_txh_hash(const mi_cls_ctx_t *c) { return (uint32_t *)(stg_tx_desc(c) + c->n_cap); }
+static uint8_t *stg_txh_done(const mi_cls_ctx_t *c) { return (uint8_t *)(stg_txh_hash(c) + c->n_cap); }
 static mi_cls_lso_desc_t *stg_lso_desc(const mi_cls_ctx_t *c) { return (mi_cls_lso_desc_t *)c->d_out; }
 static mi_cls_lso_seg_t *stg_lso_seg(const mi_cls_ctx_t *c, uint32_t n) { return (mi_cls_lso_seg_t *)(c->d_out + n); }
 static uint8_t *stg_lso_st(const mi_cls_ctx_t *c, uint32_t n) { return (uint8_t *)(c->d_len + n); }
@@ -1049,42 +1055,76 @@ extern "C" int mi_cls_chksum_insert(mi_cls_ctx_t *c, uint8_t *pkts, const uint32
 	return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
 
+extern "C" int mi_cls_tx_hash(mi_cls_ctx_t *c, uint8_t *pkts, const uint32_t *off, const uint16_t *len,
+			      const mi_cls_tx_desc_t *desc, uint32_t n, uint64_t pktout_opt, uint8_t *done,
+			      uint32_t hash_proto, uint32_t *hash_out, int chksum, void *stream);
+
+// The flow hash asked for beside (ck) or instead of the checksums
+// (mi_cls_tx_hash*); the checksum entries pass none
+struct TxHashReq {
+	uint32_t proto;
+	uint32_t *out;
+	int ck;
+};
+
+static int tx_launch(mi_cls_ctx_t *c, uint8_t *pkts, const uint32_t *off, const uint16_t *len,
+		     const mi_cls_tx_desc_t *desc, uint32_t n, uint64_t opt, uint8_t *done, const TxHashReq *hq,
+		     uint32_t *hash, hipStream_t s)
+{
+	return hq ? mi_cls_tx_hash(c, pkts, off, len, desc, n, opt, done, hq->proto, hash, hq->ck, s)
+		  : mi_cls_chksum_insert(c, pkts, off, len, desc, n, opt, done, s);
+}
+
 // A host batch on the context's stream, nothing waited for: in place when
-// everything is page-locked (`done` too, where given) and
+// everything is page-locked (`done` and the hash words too, where given) and
 // frames_padded_inside(bytes), else through the staging buffers (the frames
-// copied back whole: only checksum fields differ).
+// copied back whole: only checksum fields differ; the hash alone writes none
+// and copies none back).
 static int tx_host_launch(mi_cls_ctx_t *c, uint8_t *pkts, size_t bytes, const uint32_t *off,
 			  const uint16_t *len, const mi_cls_tx_desc_t *desc, uint32_t n, uint64_t opt,
-			  uint8_t *done)
+			  uint8_t *done, const TxHashReq *hq = nullptr)
 {
 	HIP_OK(set_device(c->device));
 	uint8_t *zp = pkts, *zn = done;
 	const uint32_t *zo = off;
 	const uint16_t *zl = len;
 	const mi_cls_tx_desc_t *zd = desc;
-	if (dev_views(zp, zo, zl, zd) && (!done || dev_views(zn)) && frames_padded_inside(off, len, n, bytes))
-		return mi_cls_chksum_insert(c, zp, zo, zl, zd, n, opt, zn, c->stream);
+	uint32_t *zh = hq ? hq->out : nullptr;
+	if (dev_views(zp, zo, zl, zd) && (!done || dev_views(zn)) && (!hq || dev_views(zh)) &&
+	    frames_padded_inside(off, len, n, bytes))
+		return tx_launch(c, zp, zo, zl, zd, n, opt, zn, hq, zh, c->stream);
 	int rc = stage_up(c, pkts, bytes, bytes, off, len, n, n);
 	if (rc)
 		return rc;
 	hipStream_t s = c->stream;
 	mi_cls_tx_desc_t *d_desc = stg_tx_desc(c);
-	uint8_t *d_done = stg_tx_done(c);
+	uint32_t *d_hash = stg_txh_hash(c);
+	uint8_t *d_done = hq ? stg_txh_done(c) : stg_tx_done(c);
 	HIP_OK(hipMemcpyAsync(d_desc, desc, n * sizeof(mi_cls_tx_desc_t), hipMemcpyHostToDevice, s));
-	rc = mi_cls_chksum_insert(c, c->d_pk, c->d_off, c->d_len, d_desc, n, opt, done ? d_done : nullptr, s);
+	rc = tx_launch(c, c->d_pk, c->d_off, c->d_len, d_desc, n, opt, done ? d_done : nullptr, hq, d_hash, s);
 	if (rc)
 		return rc;
-	HIP_OK(hipMemcpyAsync(pkts, c->d_pk, bytes, hipMemcpyDeviceToHost, s));
+	if (!hq || hq->ck)
+		HIP_OK(hipMemcpyAsync(pkts, c->d_pk, bytes, hipMemcpyDeviceToHost, s));
+	if (hq)
+		HIP_OK(hipMemcpyAsync(hq->out, d_hash, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
 	if (done)
 		HIP_OK(hipMemcpyAsync(done, d_done, n, hipMemcpyDeviceToHost, s));
 	return 0;
 }
 
+// The checks of a host entry; hq: also its hash words and protocol bits
+static bool tx_hash_req_ok(const TxHashReq *hq)
+{
+	return hq->out && ((uintptr_t)hq->out & 3u) == 0 && hq->proto != 0 && hq->proto < 64u;
+}
+
 static int tx_host_check(mi_cls_ctx_t *c, const uint8_t *pkts, size_t bytes, const uint32_t *off,
-			 const uint16_t *len, const mi_cls_tx_desc_t *desc, uint32_t n)
+			 const uint16_t *len, const mi_cls_tx_desc_t *desc, uint32_t n,
+			 const TxHashReq *hq = nullptr)
 {
 	const int rc = tx_check(c, pkts, off, len, desc, n);
-	return rc || n == 0 || frames_inside(off, len, n, bytes) ? rc : -EINVAL;
+	return rc || n == 0 || (frames_inside(off, len, n, bytes) && (!hq || tx_hash_req_ok(hq))) ? rc : -EINVAL;
 }
 
 extern "C" int mi_cls_chksum_insert_host(mi_cls_ctx_t *c, uint8_t *pkts, size_t bytes,
@@ -1113,6 +1153,78 @@ extern "C" int mi_cls_chksum_insert_host_submit(mi_cls_ctx_t *c, uint8_t *pkts, 
 }
 
 extern "C" int mi_cls_chksum_insert_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
+{
+	return feature_host_wait(c, ticket);
+}
+
+// ------------------------------------------------------- the pktin flow hash
+// (pktio/loop.c:479-530 get_dest_queue): the transmit kernel with the hash
+// step, beside the checksums (chksum != 0) or alone
+extern "C" int mi_cls_tx_hash(mi_cls_ctx_t *c, uint8_t *pkts, const uint32_t *off, const uint16_t *len,
+			      const mi_cls_tx_desc_t *desc, uint32_t n, uint64_t pktout_opt, uint8_t *done,
+			      uint32_t hash_proto, uint32_t *hash_out, int chksum, void *stream)
+{
+	const TxHashReq hq = { hash_proto, hash_out, chksum };
+	const int bad = tx_check(c, pkts, off, len, desc, n);
+	if (bad || n == 0)
+		return bad;
+	if (!tx_hash_req_ok(&hq))
+		return -EINVAL;
+	HIP_OK(set_device(c->device));
+	TxHashArgs a;
+	a.pkts = pkts;
+	a.off = off;
+	a.len = len;
+	a.desc = desc;
+	a.done = done;
+	a.n = n;
+	a.opt = (uint32_t)pktout_opt;
+	a.hash = hash_out;
+	a.hash_proto = hash_proto;
+	a.rsv = 0;
+	// the grid of mi_cls_chksum_insert
+	const uint32_t tiles = (n + WAVE - 1) / WAVE;
+	const uint32_t blocks = (tiles + TX_NW - 1) / TX_NW;
+	const uint32_t max_grid = (uint32_t)c->num_cu * 6u;
+	const int rc = mi_cls_launch_tx_hash(chksum != 0, blocks < max_grid ? blocks : max_grid,
+					     (hipStream_t)stream, a);
+	if (rc)
+		return rc;
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+// The host entries: tx_host_check / tx_host_launch with the hash request
+extern "C" int mi_cls_tx_hash_host(mi_cls_ctx_t *c, uint8_t *pkts, size_t bytes, const uint32_t *off,
+				   const uint16_t *len, const mi_cls_tx_desc_t *desc, uint32_t n, uint64_t opt,
+				   uint8_t *done, uint32_t hash_proto, uint32_t *hash_out, int chksum)
+{
+	const TxHashReq hq = { hash_proto, hash_out, chksum };
+	const int rc = tx_host_check(c, pkts, bytes, off, len, desc, n, &hq);
+	if (rc || n == 0)
+		return rc;
+	return host_run(c, nullptr, [&] {
+		return tx_host_launch(c, pkts, bytes, off, len, desc, n, opt, done, &hq);
+	});
+}
+
+extern "C" int mi_cls_tx_hash_host_submit(mi_cls_ctx_t *c, uint8_t *pkts, size_t bytes, const uint32_t *off,
+					  const uint16_t *len, const mi_cls_tx_desc_t *desc, uint32_t n,
+					  uint64_t opt, uint8_t *done, uint32_t hash_proto, uint32_t *hash_out,
+					  int chksum, uint64_t *ticket)
+{
+	if (!ticket)
+		return -EINVAL;
+	*ticket = 0;
+	const TxHashReq hq = { hash_proto, hash_out, chksum };
+	const int rc = tx_host_check(c, pkts, bytes, off, len, desc, n, &hq);
+	if (rc || n == 0)
+		return rc;
+	return host_run(c, ticket, [&] {
+		return tx_host_launch(c, pkts, bytes, off, len, desc, n, opt, done, &hq);
+	});
+}
+
+extern "C" int mi_cls_tx_hash_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
 {
 	return feature_host_wait(c, ticket);
 }

@@ -2778,8 +2778,18 @@ struct TxArgs {
 	uint32_t n;
 	uint32_t opt;           // odp_pktout_config_opt_t.all_bits
 };
+// with the pktin flow hash (mi_cls_tx_hash): arguments of their own, so the
+// checksum kernel's stay as they are
+struct TxHashArgs : TxArgs {
+	uint32_t *hash;         // the flow hash per packet
+	uint32_t hash_proto;    // odp_pktin_hash_proto_t.all_bits
+	uint32_t rsv;
+};
 #define TX_NW 4             // waves per block
 int mi_cls_launch_tx(unsigned grid, hipStream_t st, const TxArgs &a);
+// the same kernel with the pktin flow hash (mi_cls_tx_hash; mi_cls_kh.hip):
+// beside the checksums (ck) or alone
+int mi_cls_launch_tx_hash(bool ck, unsigned grid, hipStream_t st, const TxHashArgs &a);
 
 // the parse on its own (mi_cls_parse; kernel: mi_cls_parse_dev.h,
 // mi_cls_kp.hip).  grid == 0: preload only.

@@ -12,11 +12,11 @@ int mi_cls_launch_tx(unsigned grid, hipStream_t st, const TxArgs &a)
 #else
 	if (grid == 0) {   // preload (mi_cls_ctx_create)
 		hipFuncAttributes fa;
-		return hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&mi_cls_tx_kernel)) ==
+		return hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&mi_cls_tx_kernel<TX_M_CK, TxArgs>)) ==
 		       hipSuccess ? 0 : -EIO;
 	}
 	void *args[] = { (void *)&a };
-	return hipLaunchKernel(reinterpret_cast<const void *>(&mi_cls_tx_kernel), dim3(grid),
+	return hipLaunchKernel(reinterpret_cast<const void *>(&mi_cls_tx_kernel<TX_M_CK, TxArgs>), dim3(grid),
 			       dim3(TX_NW * WAVE), args, 0, st) == hipSuccess ? 0 : -EIO;
 #endif
 }

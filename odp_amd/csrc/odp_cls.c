@@ -1653,6 +1653,20 @@ int odp_amd_cls_chksum_insert_host(odp_pktio_t h, uint8_t *pkts, size_t bytes, c
 	return rc ? rc : mi_cls_chksum_insert_host(tctx, pkts, bytes, off, len, desc, n, pktout_opt, done);
 }
 
+/* The same launch with the pktin flow hash of every packet
+ * (mi_cls_tx_hash_host; chksum 0: the hash alone). */
+int odp_amd_cls_tx_hash_host(odp_pktio_t h, uint8_t *pkts, size_t bytes, const uint32_t *off,
+			     const uint16_t *len, const mi_cls_tx_desc_t *desc, uint32_t n,
+			     uint64_t pktout_opt, uint8_t *done, uint32_t hash_proto, uint32_t *hash_out,
+			     int chksum)
+{
+	mi_cls_ctx_t *tctx;
+	const int rc = tx_ctx(h, &tctx);
+
+	return rc ? rc : mi_cls_tx_hash_host(tctx, pkts, bytes, off, len, desc, n, pktout_opt, done, hash_proto,
+					     hash_out, chksum);
+}
+
 /* LSO segmentation of a send call (mi_cls_lso_segment_host) on the pktio's
  * transmit context, as odp_amd_cls_chksum_insert_host. */
 int odp_amd_cls_lso_segment_host(odp_pktio_t h, uint8_t *buf, size_t bytes, const uint32_t *off,

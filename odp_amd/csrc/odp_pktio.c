@@ -39,6 +39,7 @@
 #include <time.h>
 
 #include "odp_rt_internal.h"
+#include "odp_txq.h"
 #include "mi_cls.h"
 
 static int rx_prof = -1;   /* ODP_AMD_RX_PROF set: receive-path phase times */
@@ -164,8 +165,18 @@ typedef struct {
 	odp_pktio_param_t param;
 	odp_pktio_config_t config;
 	odp_pktin_queue_param_t inq_param;
-	odp_queue_t inq;            /* SCHED / QUEUE mode input queue */
+	odp_queue_t inq[ODP_PKTIN_MAX_QUEUES];   /* SCHED / QUEUE mode input queues */
 	int inq_configured;
+	uint32_t num_in;            /* input queues (0 until configured: one) */
+	uint32_t hash_proto;        /* pktin hash: hash_enable ? hash_proto.all_bits : 0 */
+	uint32_t rx_idx;            /* input queue of the receive call in progress (rxl) */
+	/* per-queue counters (loop.c:781-805): pktio_stats stays their sum */
+	struct {
+		odp_atomic_u64_t octets, packets, discards, errors;
+	} inq_st[ODP_PKTIN_MAX_QUEUES];
+	struct {
+		odp_atomic_u64_t octets, packets;
+	} outq_st[ODP_PKTOUT_MAX_QUEUES];
 	uint32_t num_out;
 	int state;
 	int cls_enabled;
@@ -181,8 +192,8 @@ typedef struct {
 	uint32_t nframes, next;
 	int loops, loop_cnt, eof;
 	FILE *tx;
-	/* loop */
-	odp_queue_t loopq;
+	/* loop: one loop queue per input queue */
+	odp_queue_t loopq[ODP_PKTIN_MAX_QUEUES];
 	size_t fbuf_bytes;      /* frame store size incl. 64 B of zero padding */
 	int fbuf_pinned;        /* page-locked: the GPU reads frames in place */
 	/* GPU bursts: RX_SETS staging sets, so one burst is staged while older
@@ -200,6 +211,7 @@ typedef struct {
 	 * of LSO (an odp_pktout_send_lso call), both under txl */
 	pthread_mutex_t txl;    /* held across the kernel's launch and wait */
 	gather_t txg, lsog;
+	uint64_t txq_bursts;    /* sends whose launch computed the flow hash */
 	uint64_t prof[16];      /* ODP_AMD_RX_PROF: ns staging / classifying / delivering, bursts,
 				 * then of delivering: ns preparing / enqueueing, TSC ticks in
 				 * packet allocation / frame copies; GPU delivery: ns deciding +
@@ -555,6 +567,46 @@ void odp_pktio_config_init(odp_pktio_config_t *c)
 	c->reassembly.max_num_frags = 2;
 }
 
+static void queue_drain_destroy(odp_queue_t *q)
+{
+	odp_event_t ev[64];
+	int n;
+
+	if (*q == ODP_QUEUE_INVALID)
+		return;
+	while ((n = rt_queue_deq_multi_raw((rt_queue_t *)(void *)*q, ev, 64)) > 0)
+		odp_event_free_multi(ev, n);
+	odp_queue_destroy(*q);
+	*q = ODP_QUEUE_INVALID;
+}
+
+/* The loop queues of a loop pktio, one per input queue (loop.c:172-206):
+ * those it has are drained and destroyed, then n are created, queue i
+ * holding at most size[i] events (0, or size NULL: no bound). */
+static int loopqs_create(rt_pktio_t *e, uint32_t n, const uint32_t size[])
+{
+	for (uint32_t i = 0; i < ODP_PKTIN_MAX_QUEUES; i++)
+		queue_drain_destroy(&e->loopq[i]);
+	for (uint32_t i = 0; i < n; i++) {
+		odp_queue_param_t qp;
+		char qn[ODP_QUEUE_NAME_LEN];
+
+		odp_queue_param_init(&qp);
+		if (i == 0)
+			snprintf(qn, sizeof(qn), "%.20s_loopq", e->name);
+		else
+			snprintf(qn, sizeof(qn), "%.20s_loopq-%u", e->name, i);
+		e->loopq[i] = odp_queue_create(qn, &qp);
+		if (e->loopq[i] == ODP_QUEUE_INVALID) {
+			while (i--)
+				queue_drain_destroy(&e->loopq[i]);
+			return -1;
+		}
+		((rt_queue_t *)(void *)e->loopq[i])->limit = size ? size[i] : 0;
+	}
+	return 0;
+}
+
 odp_pktio_t odp_pktio_open(const char *name, odp_pool_t pool, const odp_pktio_param_t *param)
 {
 	odp_pktio_param_t def;
@@ -631,13 +683,7 @@ odp_pktio_t odp_pktio_open(const char *name, odp_pool_t pool, const odp_pktio_pa
 		return ODP_PKTIO_INVALID;
 	}
 	if (drv == DRV_LOOP) {
-		odp_queue_param_t qp;
-		char qn[ODP_QUEUE_NAME_LEN];
-
-		odp_queue_param_init(&qp);
-		snprintf(qn, sizeof(qn), "%.20s_loopq", name);
-		e->loopq = odp_queue_create(qn, &qp);
-		if (e->loopq == ODP_QUEUE_INVALID) {
+		if (loopqs_create(e, 1, NULL)) {
 			e->used = 0;
 			odp_amd_cls_pktio_destroy(h);
 			return ODP_PKTIO_INVALID;
@@ -663,10 +709,27 @@ int odp_pktio_capability(odp_pktio_t h, odp_pktio_capability_t *c)
 	if (!e || !c)
 		return -1;
 	memset(c, 0, sizeof(*c));
-	c->max_input_queues = 1;
+	/* loop.c:672-684: one loop queue per input queue, flows spread over them
+	 * by the pktin hash; their size is configurable in DIRECT mode */
+	c->max_input_queues = e->drv == DRV_LOOP ? ODP_PKTIN_MAX_QUEUES : 1;
 	c->max_output_queues = e->drv == DRV_LOOP ? ODP_PKTOUT_MAX_QUEUES : 1;
-	c->max_input_queue_size = 0;
+	c->min_input_queue_size = e->drv == DRV_LOOP ? 1 : 0;
+	c->max_input_queue_size = e->drv == DRV_LOOP ? RT_LOOP_MAX_QUEUE_SIZE : 0;
 	c->max_output_queue_size = 0;
+	c->stats.pktio.counter.in_octets = 1;
+	c->stats.pktio.counter.in_packets = 1;
+	c->stats.pktio.counter.in_errors = 1;
+	c->stats.pktio.counter.in_discards = 1;
+	c->stats.pktio.counter.out_octets = 1;
+	c->stats.pktio.counter.out_packets = 1;
+	if (e->drv == DRV_LOOP) {   /* loop.c:723-728 */
+		c->stats.pktin_queue.counter.octets = 1;
+		c->stats.pktin_queue.counter.packets = 1;
+		c->stats.pktin_queue.counter.errors = 1;
+		c->stats.pktin_queue.counter.discards = 1;
+		c->stats.pktout_queue.counter.octets = 1;
+		c->stats.pktout_queue.counter.packets = 1;
+	}
 	odp_pktio_config_init(&c->config);
 	c->config.parser.layer = ODP_PROTO_LAYER_ALL;
 	c->config.pktin.all_bits = RT_PKTIN_OPT_MASK;
@@ -735,35 +798,77 @@ int odp_pktin_queue_config(odp_pktio_t h, const odp_pktin_queue_param_t *param)
 	}
 	if (e->param.in_mode == ODP_PKTIN_MODE_DISABLED)
 		return -1;
-	if (param->num_queues > 1 || (param->num_queues == 0 && !param->classifier_enable)) {
-		RT_ERR("pktio %s: %u input queues requested, 1 supported\n", e->name,
-		       param->num_queues);
+	/* odp_packet_io.c:1984-2014: the classifier delivers by CoS, so with it
+	 * the driver has one input queue whatever num_queues says */
+	odp_pktio_capability_t capa;
+	const uint32_t nq = param->classifier_enable ? 1 : param->num_queues;
+	const int direct = e->param.in_mode == ODP_PKTIN_MODE_DIRECT;
+
+	if (odp_pktio_capability(h, &capa))
 		return -1;
+	if (nq == 0 || nq > capa.max_input_queues) {
+		RT_ERR("pktio %s: %u input queues requested, 1 .. %u supported\n", e->name,
+		       param->num_queues, capa.max_input_queues);
+		return -1;
+	}
+	for (uint32_t i = 0; i < nq && direct; i++) {   /* :2017-2036 */
+		const uint32_t qs = param->queue_size[i];
+
+		if (qs && (qs < capa.min_input_queue_size || qs > capa.max_input_queue_size)) {
+			RT_ERR("pktio %s: input queue size %u not supported\n", e->name, qs);
+			return -1;
+		}
 	}
 	if (param->vector.enable) {
 		RT_ERR("pktio %s: packet vectors are not supported\n", e->name);
 		return -1;
 	}
-	if (e->inq != ODP_QUEUE_INVALID) {
-		odp_queue_destroy(e->inq);
-		e->inq = ODP_QUEUE_INVALID;
-	}
+	/* a re-configuration may change the queue count: no burst of the old
+	 * queues stays behind, and the loop queues are made anew (loop.c:172-227) */
+	odp_spinlock_lock(&e->rxl);
+	for (uint32_t i = 0; i < ODP_PKTIN_MAX_QUEUES; i++)
+		queue_drain_destroy(&e->inq[i]);
 	e->inq_param = *param;
+	e->inq_param.num_queues = nq;
+	e->inq_param.queue_param_ovr = NULL;   /* the caller's array: used below only */
 	e->cls_enabled = param->classifier_enable;
-	if (e->param.in_mode == ODP_PKTIN_MODE_SCHED || e->param.in_mode == ODP_PKTIN_MODE_QUEUE) {
-		odp_queue_param_t qp = param->queue_param;
+	e->num_in = 0;
+	e->hash_proto = param->hash_enable ? param->hash_proto.all_bits & 63u : 0;
+	if (e->drv == DRV_LOOP && loopqs_create(e, nq, direct ? param->queue_size : NULL)) {
+		odp_spinlock_unlock(&e->rxl);
+		return -1;
+	}
+	for (uint32_t i = 0; i < nq && !direct; i++) {   /* :2093-2140 */
+		odp_queue_param_t qp;
 		char qn[ODP_QUEUE_NAME_LEN];
 
+		/* a queue count the classifier forced to 1: the default queue, as
+		 * the reference gives every classifier pktin queue (:2109-2110);
+		 * a classifier config that asked for one queue keeps its
+		 * queue_param, as before */
+		if (param->classifier_enable && nq != param->num_queues) {
+			odp_queue_param_init(&qp);
+		} else {
+			qp = param->queue_param;
+			if (!param->classifier_enable && param->queue_param_ovr)
+				qp.sched.group = param->queue_param_ovr[i].group;
+		}
 		qp.type = e->param.in_mode == ODP_PKTIN_MODE_SCHED ? ODP_QUEUE_TYPE_SCHED
 								    : ODP_QUEUE_TYPE_PLAIN;
-		snprintf(qn, sizeof(qn), "odp-pktin-%d-0", (int)((uintptr_t)h - 1));
-		e->inq = odp_queue_create(qn, &qp);
-		if (e->inq == ODP_QUEUE_INVALID)
+		snprintf(qn, sizeof(qn), "odp-pktin-%d-%u", (int)((uintptr_t)h - 1), i);
+		e->inq[i] = odp_queue_create(qn, &qp);
+		if (e->inq[i] == ODP_QUEUE_INVALID) {
+			while (i--)
+				queue_drain_destroy(&e->inq[i]);
+			odp_spinlock_unlock(&e->rxl);
 			return -1;
+		}
 		if (e->param.in_mode == ODP_PKTIN_MODE_QUEUE)
-			((rt_queue_t *)(void *)e->inq)->pktin_idx = (int)(uintptr_t)h;
+			((rt_queue_t *)(void *)e->inq[i])->pktin_idx = (int)(uintptr_t)h;
 	}
+	e->num_in = nq;
 	e->inq_configured = 1;
+	odp_spinlock_unlock(&e->rxl);
 	return 0;
 }
 
@@ -788,12 +893,14 @@ int odp_pktin_queue(odp_pktio_t h, odp_pktin_queue_t q[], int num)
 
 	if (!e || e->param.in_mode != ODP_PKTIN_MODE_DIRECT)
 		return -1;
-	if (num > 0 && q) {
-		q[0].q = (_odp_pktin_hdl_t)(uintptr_t)h;
-		q[0].index = 0;
-		q[0].pktio = h;
+	const int nq = e->num_in ? (int)e->num_in : 1;
+
+	for (int i = 0; q && i < num && i < nq; i++) {
+		q[i].q = (_odp_pktin_hdl_t)(uintptr_t)h;
+		q[i].index = i;
+		q[i].pktio = h;
 	}
-	return 1;
+	return nq;
 }
 
 int odp_pktin_event_queue(odp_pktio_t h, odp_queue_t q[], int num)
@@ -803,9 +910,13 @@ int odp_pktin_event_queue(odp_pktio_t h, odp_queue_t q[], int num)
 	if (!e || (e->param.in_mode != ODP_PKTIN_MODE_SCHED &&
 		   e->param.in_mode != ODP_PKTIN_MODE_QUEUE))
 		return -1;
-	if (num > 0 && q)
-		q[0] = e->inq;
-	return e->inq != ODP_QUEUE_INVALID ? 1 : 0;
+	int nq = 0;
+
+	while (nq < ODP_PKTIN_MAX_QUEUES && e->inq[nq] != ODP_QUEUE_INVALID)
+		nq++;
+	for (int i = 0; q && i < num && i < nq; i++)
+		q[i] = e->inq[i];
+	return nq;
 }
 
 int odp_pktout_queue(odp_pktio_t h, odp_pktout_queue_t q[], int num)
@@ -879,7 +990,8 @@ int odp_pktio_start(odp_pktio_t h)
 	}
 	/* pktout checksum insertion configured: its GPU context before traffic,
 	 * also when the input side needs none */
-	if (e->drv == DRV_LOOP && (e->config.pktout.all_bits & RT_PKTOUT_OPT_MASK)) {
+	if (e->drv == DRV_LOOP && ((e->config.pktout.all_bits & RT_PKTOUT_OPT_MASK) ||
+				   (e->hash_proto && e->num_in > 1))) {
 		int rc = odp_amd_cls_chksum_insert_host(h, NULL, 0, NULL, NULL, NULL, 0, 0, NULL);
 
 		if (rc) {
@@ -960,21 +1072,9 @@ int odp_pktio_close(odp_pktio_t h)
 			e->prof[3], e->prof[0], e->prof[1], e->prof[2], e->prof[4], e->prof[5], e->prof[6],
 			e->prof[7], e->prof[11], e->prof[8], e->prof[12], e->prof[9], e->prof[10], e->prof[13],
 			e->prof[14], e->prof[15]);
-	if (e->inq != ODP_QUEUE_INVALID) {
-		odp_event_t ev[64];
-		int n;
-
-		while ((n = rt_queue_deq_multi_raw((rt_queue_t *)(void *)e->inq, ev, 64)) > 0)
-			odp_event_free_multi(ev, n);
-		odp_queue_destroy(e->inq);
-	}
-	if (e->loopq != ODP_QUEUE_INVALID) {
-		odp_event_t ev[64];
-		int n;
-
-		while ((n = rt_queue_deq_multi_raw((rt_queue_t *)(void *)e->loopq, ev, 64)) > 0)
-			odp_event_free_multi(ev, n);
-		odp_queue_destroy(e->loopq);
+	for (uint32_t i = 0; i < ODP_PKTIN_MAX_QUEUES; i++) {
+		queue_drain_destroy(&e->inq[i]);
+		queue_drain_destroy(&e->loopq[i]);
 	}
 	if (e->tx)
 		fclose(e->tx);
@@ -1484,7 +1584,7 @@ static int loop_stage_hdrs(rt_pktio_t *e, rx_set_t *s, uint32_t n)
  * at delivery.  Other pcap frames are copied into the stage (64 B aligned
  * offsets) and allocated later, directly from the final pool; loop frames
  * keep their packets in s->pk.  Returns the frame count. */
-static int stage_frames(rt_pktio_t *e, rx_set_t *s, uint32_t max)
+static int stage_frames(rt_pktio_t *e, rx_set_t *s, uint32_t max, uint32_t idx)
 {
 	uint32_t n = 0;
 	size_t off = 0;
@@ -1539,7 +1639,7 @@ static int stage_frames(rt_pktio_t *e, rx_set_t *s, uint32_t max)
 		while (n < max) {
 			odp_event_t *ev = (odp_event_t *)(void *)(s->pk + n);
 			int want = (int)(max - n);
-			int got = rt_queue_deq_multi_raw((rt_queue_t *)(void *)e->loopq, ev, want);
+			int got = rt_queue_deq_multi_raw((rt_queue_t *)(void *)e->loopq[idx], ev, want);
 
 			if (got <= 0)
 				break;
@@ -1566,13 +1666,13 @@ static int stage_frames(rt_pktio_t *e, rx_set_t *s, uint32_t max)
 }
 
 /* more frames ready at the driver right now (a burst in flight can wait) */
-static int rx_more(rt_pktio_t *e)
+static int rx_more(rt_pktio_t *e, uint32_t idx)
 {
 	if (e->drv == DRV_PCAP)
 		return e->nframes && !e->eof &&
 		       (e->next < e->nframes || e->loops == 0 || e->loop_cnt + 1 < e->loops);
 	if (e->drv == DRV_LOOP)
-		return ((rt_queue_t *)(void *)e->loopq)->count > 0;
+		return ((rt_queue_t *)(void *)e->loopq[idx])->count > 0;
 	return 0;
 }
 
@@ -1716,6 +1816,14 @@ static inline void rx_cnt_flush(rt_pktio_t *e, const rx_cnt_t *c)
 		odp_atomic_add_u64(&e->in_discards, c->in_discards);
 	odp_atomic_add_u64(&e->in_octets, c->octets);
 	odp_atomic_add_u64(&e->in_packets, c->packets);
+	/* and to the input queue the burst was received on (several queues: a
+	 * receive call leaves no burst in flight, so it is the call's queue) */
+	if (c->in_errors)
+		odp_atomic_add_u64(&e->inq_st[e->rx_idx].errors, c->in_errors);
+	if (c->in_discards)
+		odp_atomic_add_u64(&e->inq_st[e->rx_idx].discards, c->in_discards);
+	odp_atomic_add_u64(&e->inq_st[e->rx_idx].octets, c->octets);
+	odp_atomic_add_u64(&e->inq_st[e->rx_idx].packets, c->packets);
 }
 
 /* Packet metadata of a delivered frame from its record. */
@@ -2981,9 +3089,13 @@ static int rxc_end(rt_pktio_t *e, rx_set_t *s, odp_packet_t out[], int max_out)
  * 4096-frame burst).  A call with nothing more at the driver delivers
  * everything, oldest first.  Unclassified packets are returned in out[] (at
  * most max_out); classified ones are enqueued to their CoS queues. */
-static int pktio_recv(rt_pktio_t *e, odp_packet_t out[], int max_out)
+static int pktio_recv(rt_pktio_t *e, uint32_t idx, odp_packet_t out[], int max_out)
 {
 	rx_set_t *s = rx_age(e, 0);
+
+	/* several input queues exist only with the classifier off, where a call
+	 * leaves no burst in flight (pipe is 0): the burst sets stay per pktio */
+	e->rx_idx = idx;
 	long pending_n = 0;   /* frames staged, not yet taken from pools */
 	int in_flight = 0;
 
@@ -3018,7 +3130,7 @@ static int pktio_recv(rt_pktio_t *e, odp_packet_t out[], int max_out)
 		}
 	}
 	uint64_t t0 = prof_ns();
-	int n = stage_frames(e, s, burst);
+	int n = stage_frames(e, s, burst, idx);
 	uint64_t t1 = prof_ns();
 
 	e->prof[0] += t1 - t0;
@@ -3044,7 +3156,7 @@ static int pktio_recv(rt_pktio_t *e, odp_packet_t out[], int max_out)
 		num_rx += rx_dlv_end(e, z, out, max_out);
 	/* only a burst really in flight streams (a multi-GPU pktio's submit
 	 * completes before it returns: ticket 0) */
-	if (n > 0 && pipe && (s->ticket || s->chain) && rx_more(e)) {
+	if (n > 0 && pipe && (s->ticket || s->chain) && rx_more(e, idx)) {
 		rx_set_t *q = rx_age(e, RX_CLS_DEPTH);
 
 		if (q->pending)
@@ -3075,27 +3187,36 @@ static int pktio_recv(rt_pktio_t *e, odp_packet_t out[], int max_out)
 static int poll_into_inq(rt_pktio_t *e)
 {
 	odp_packet_t pk[RX_BURST_DEFAULT];
-	int n;
+	int total = 0;
 
-	if (!odp_spinlock_trylock(&e->rxl))
-		return 0;
-	if (e->state != ST_STARTED) {
+	/* every input queue in turn, each into its own event queue */
+	for (uint32_t idx = 0; idx == 0 || idx < e->num_in; idx++) {
+		odp_queue_t inq;
+		int n;
+
+		if (!odp_spinlock_trylock(&e->rxl))
+			return total;
+		if (e->state != ST_STARTED || idx >= (e->num_in ? e->num_in : 1u)) {
+			odp_spinlock_unlock(&e->rxl);
+			return total;
+		}
+		inq = e->inq[idx];
+		n = pktio_recv(e, idx, pk, RX_BURST_DEFAULT);
 		odp_spinlock_unlock(&e->rxl);
-		return 0;
-	}
-	n = pktio_recv(e, pk, RX_BURST_DEFAULT);
-	odp_spinlock_unlock(&e->rxl);
-	if (n > 0) {
-		int r = odp_queue_enq_multi(e->inq, (const odp_event_t *)(void *)pk, n);
+		if (n > 0) {
+			int r = odp_queue_enq_multi(inq, (const odp_event_t *)(void *)pk, n);
 
-		if (r < 0)
-			r = 0;
-		if (r < n) {
-			odp_packet_free_multi(&pk[r], n - r);
-			odp_atomic_add_u64(&e->in_discards, (uint64_t)(n - r));
+			if (r < 0)
+				r = 0;
+			if (r < n) {
+				odp_packet_free_multi(&pk[r], n - r);
+				odp_atomic_add_u64(&e->in_discards, (uint64_t)(n - r));
+				odp_atomic_add_u64(&e->inq_st[idx].discards, (uint64_t)(n - r));
+			}
+			total += n;
 		}
 	}
-	return n;
+	return total;
 }
 
 int rt_pktio_sched_poll(void)
@@ -3130,7 +3251,10 @@ int odp_pktin_recv(odp_pktin_queue_t q, odp_packet_t pkts[], int num)
 	if (e->state != ST_STARTED)
 		return 0;
 	odp_spinlock_lock(&e->rxl);
-	n = e->state == ST_STARTED ? pktio_recv(e, pkts, num) : 0;
+	if (q.index < 0 || (uint32_t)q.index >= (e->num_in ? e->num_in : 1u))
+		n = -1;
+	else
+		n = e->state == ST_STARTED ? pktio_recv(e, (uint32_t)q.index, pkts, num) : 0;
 	odp_spinlock_unlock(&e->rxl);
 	return n;
 }
@@ -3282,10 +3406,20 @@ static void tx_free(rt_pktio_t *e)
  * goes through a page-locked bounce buffer.  Waits for the kernel.  The
  * packets' override bits stay as they are (a packet the loop queue does not
  * take goes back to the application with them): the loop receive resets them
- * (packet_parse_reset(.., 1), loop.c:308).  0, or -1. */
-static int tx_chksum(rt_pktio_t *e, const odp_packet_t pkts[], int num)
+ * (packet_parse_reset(.., 1), loop.c:308).  0, or -1.
+ *
+ * dst != NULL (several input queues): dst[i] becomes the loop queue of packet
+ * i (get_dest_queue, loop.c:479-530, 582).  With the pktin hash off that is
+ * host arithmetic and nothing above changes.  With it on, the call's one
+ * launch also computes every packet's flow hash (mi_cls_tx_hash_host: the
+ * hash alone when nothing asks for a checksum, writing no frame byte): the
+ * descriptors then carry the packet's has_udp / tcp / ipv4 / ipv6 flags, the
+ * hash words are one more page-locked array of the gather, and the modulo
+ * is taken here. */
+static int tx_chksum(rt_pktio_t *e, const odp_packet_t pkts[], int num, uint8_t *dst, uint32_t index)
 {
 	const uint64_t opt = e->config.pktout.all_bits & RT_PKTOUT_OPT_MASK;
+	const uint32_t hp = dst ? e->hash_proto : 0;
 	int want = (opt & 0xF0u) != 0;
 
 	for (int i = 0; !want && i < num; i++) {
@@ -3294,7 +3428,9 @@ static int tx_chksum(rt_pktio_t *e, const odp_packet_t pkts[], int num)
 		want |= (f & (MI_CLS_TXF_L3_SET | MI_CLS_TXF_L3)) == (MI_CLS_TXF_L3_SET | MI_CLS_TXF_L3) ||
 			(f & (MI_CLS_TXF_L4_SET | MI_CLS_TXF_L4)) == (MI_CLS_TXF_L4_SET | MI_CLS_TXF_L4);
 	}
-	if (!want)
+	if (!hp && dst)
+		txq_pick(NULL, (uint32_t)num, index, e->num_in, dst);
+	if (!want && !hp)
 		return 0;
 	const uint32_t n = (uint32_t)num;
 	int rc = -1;
@@ -3302,17 +3438,25 @@ static int tx_chksum(rt_pktio_t *e, const odp_packet_t pkts[], int num)
 	gather_t *g = &e->txg;
 
 	pthread_mutex_lock(&e->txl);
-	if (gather_begin(g, n, sizeof(mi_cls_tx_desc_t) + sizeof(uint32_t) + sizeof(uint16_t), 4096))
+	if (gather_begin(g, n, sizeof(mi_cls_tx_desc_t) + 2 * sizeof(uint32_t) + sizeof(uint16_t), 4096))
 		goto out;
 	mi_cls_tx_desc_t *desc = (mi_cls_tx_desc_t *)(void *)g->arr;
 	uint32_t *off = (uint32_t *)(void *)(desc + g->cap);
-	uint16_t *len = (uint16_t *)(void *)(off + g->cap);
+	uint32_t *hash = off + g->cap;
+	uint16_t *len = (uint16_t *)(void *)(hash + g->cap);
 
 	for (uint32_t i = 0; i < n; i++) {
 		const pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
+		/* input flags 13 / 14 / 22 / 23: has_ipv4 / ipv6 / udp / tcp */
+		const uint32_t meta = !hp ? 0u
+			: (((h->in_flags >> 22) & 1u) ? MI_CLS_TXF_UDP : 0u) |
+			  (((h->in_flags >> 23) & 1u) ? MI_CLS_TXF_TCP : 0u) |
+			  (((h->in_flags >> 13) & 1u) ? MI_CLS_TXF_IPV4 : 0u) |
+			  (((h->in_flags >> 14) & 1u) ? MI_CLS_TXF_IPV6 : 0u);
 
 		len[i] = (uint16_t)(h->len > GATHER_LEN_MAX ? GATHER_LEN_MAX : h->len);
-		desc[i] = (mi_cls_tx_desc_t){ .l3 = h->l3, .l4 = h->l4, .flags = (uint8_t)(h->tx_ck & 0xFu) };
+		desc[i] = (mi_cls_tx_desc_t){ .l3 = h->l3, .l4 = h->l4,
+					      .flags = (uint8_t)((h->tx_ck & 0xFu) | meta) };
 		off[i] = gather_place(g, h->head + h->data_off, len[i], 16, pkt_pool_pinned(h));
 	}
 	const int bounce = gather_layout(g);
@@ -3325,13 +3469,20 @@ static int tx_chksum(rt_pktio_t *e, const odp_packet_t pkts[], int num)
 		off[i] = gather_step(g, len[i]);
 		memcpy(g->stage + off[i], h->head + h->data_off, len[i]);
 	}
-	rc = odp_amd_cls_chksum_insert_host(e->hdl, g->base, g->bytes, off, len, desc, n, opt, NULL);
+	rc = hp ? odp_amd_cls_tx_hash_host(e->hdl, g->base, g->bytes, off, len, desc, n, opt, NULL, hp, hash,
+					   want)
+		: odp_amd_cls_chksum_insert_host(e->hdl, g->base, g->bytes, off, len, desc, n, opt, NULL);
 	if (rc) {
-		RT_ERR("pktio %s: pktout checksum insertion failed (%s)\n", e->name, mi_cls_strerror(rc));
+		RT_ERR("pktio %s: pktout %s failed (%s)\n", e->name, hp ? "flow hash" : "checksum insertion",
+		       mi_cls_strerror(rc));
 		rc = -1;
 		goto out;
 	}
-	for (uint32_t i = 0; bounce && i < n; i++) {
+	if (hp) {
+		txq_pick(hash, n, index, e->num_in, dst);
+		e->txq_bursts++;
+	}
+	for (uint32_t i = 0; bounce && want && i < n; i++) {
 		pkt_hdr_t *h = rt_pkt_hdr(pkts[i]);
 
 		memcpy(h->head + h->data_off, g->stage + off[i], len[i]);
@@ -3450,6 +3601,49 @@ void odp_amd_packet_parse_stats(uint64_t *calls, uint64_t *bounced)
 	pthread_mutex_unlock(&PRS.lock);
 }
 
+/* A send on a loop pktio with several input queues (loopback_send,
+ * loop.c:554-598): the call's one launch (checksums, flow hash), then the
+ * packets in arrival order as runs of equal destination queue, one enqueue
+ * per run, up to the first run not taken whole.  The number of leading
+ * packets sent; the others stay with the caller. */
+struct loop_enq {
+	rt_pktio_t *e;
+	const odp_packet_t *pkts;
+};
+
+static int loop_enq_run(void *arg, uint32_t queue, uint32_t first, uint32_t count)
+{
+	const struct loop_enq *a = arg;
+
+	return odp_queue_enq_multi(a->e->loopq[queue], (const odp_event_t *)(const void *)(a->pkts + first),
+				   (int)count);
+}
+
+static int loop_send_queues(rt_pktio_t *e, uint32_t oq, const odp_packet_t pkts[], int num)
+{
+	uint8_t small[1024];
+	uint8_t *dst = (size_t)num <= sizeof(small) ? small : malloc((size_t)num);
+	struct loop_enq a = { e, pkts };
+	int sent = -1;
+
+	if (!dst)
+		return -1;
+	if (tx_chksum(e, pkts, num, dst, oq) == 0) {
+		uint64_t octets = 0;
+
+		sent = (int)txq_send_runs(dst, (uint32_t)num, loop_enq_run, &a);
+		for (int i = 0; i < sent; i++)
+			octets += odp_packet_len(pkts[i]);
+		odp_atomic_add_u64(&e->out_packets, (uint64_t)sent);
+		odp_atomic_add_u64(&e->out_octets, octets);
+		odp_atomic_add_u64(&e->outq_st[oq].packets, (uint64_t)sent);
+		odp_atomic_add_u64(&e->outq_st[oq].octets, octets);
+	}
+	if (dst != small)
+		free(dst);
+	return sent;
+}
+
 int odp_pktout_send(odp_pktout_queue_t q, const odp_packet_t pkts[], int num)
 {
 	rt_pktio_t *e = get_pk(q.pktio);
@@ -3458,19 +3652,28 @@ int odp_pktout_send(odp_pktout_queue_t q, const odp_packet_t pkts[], int num)
 		return -1;
 	if (e->state != ST_STARTED)
 		return -1;
-	if (e->drv == DRV_LOOP && num > 0 && tx_chksum(e, pkts, num))
+	const uint32_t oq = (uint32_t)q.index < ODP_PKTOUT_MAX_QUEUES ? (uint32_t)q.index : 0;
+
+	if (e->drv == DRV_LOOP && e->num_in > 1 && num > 0)
+		return loop_send_queues(e, oq, pkts, num);
+	if (e->drv == DRV_LOOP && num > 0 && tx_chksum(e, pkts, num, NULL, 0))
 		return -1;
 	uint64_t octets = 0;
 
 	for (int i = 0; i < num; i++)
 		octets += odp_packet_len(pkts[i]);
 	if (e->drv == DRV_LOOP) {
-		int r = odp_queue_enq_multi(e->loopq, (const odp_event_t *)(const void *)pkts, num);
+		int r = odp_queue_enq_multi(e->loopq[0], (const odp_event_t *)(const void *)pkts, num);
 
 		if (r < 0)
 			return -1;
+		/* a sized loop queue may take fewer: only what was sent counts */
+		for (int i = r; i < num; i++)
+			octets -= odp_packet_len(pkts[i]);
 		odp_atomic_add_u64(&e->out_packets, (uint64_t)r);
 		odp_atomic_add_u64(&e->out_octets, octets);
+		odp_atomic_add_u64(&e->outq_st[oq].packets, (uint64_t)r);
+		odp_atomic_add_u64(&e->outq_st[oq].octets, octets);
 		return r;
 	}
 	for (int i = 0; i < num; i++) {
@@ -3480,6 +3683,8 @@ int odp_pktout_send(odp_pktout_queue_t q, const odp_packet_t pkts[], int num)
 	}
 	odp_atomic_add_u64(&e->out_packets, (uint64_t)num);
 	odp_atomic_add_u64(&e->out_octets, octets);
+	odp_atomic_add_u64(&e->outq_st[oq].packets, (uint64_t)num);
+	odp_atomic_add_u64(&e->outq_st[oq].octets, octets);
 	return num;
 }
 
@@ -3988,6 +4193,64 @@ int odp_pktio_stats_reset(odp_pktio_t h)
 	odp_atomic_init_u64(&e->out_octets, 0);
 	odp_atomic_init_u64(&e->out_packets, 0);
 	odp_atomic_init_u64(&e->out_discards, 0);
+	for (int i = 0; i < ODP_PKTIN_MAX_QUEUES; i++) {
+		odp_atomic_init_u64(&e->inq_st[i].octets, 0);
+		odp_atomic_init_u64(&e->inq_st[i].packets, 0);
+		odp_atomic_init_u64(&e->inq_st[i].discards, 0);
+		odp_atomic_init_u64(&e->inq_st[i].errors, 0);
+	}
+	for (int i = 0; i < ODP_PKTOUT_MAX_QUEUES; i++) {
+		odp_atomic_init_u64(&e->outq_st[i].octets, 0);
+		odp_atomic_init_u64(&e->outq_st[i].packets, 0);
+	}
+	return 0;
+}
+
+/* Per-queue counters (odp_packet_io.c:2390-2470 over loop.c:781-805) */
+static int pktin_stats_of(rt_pktio_t *e, int idx, odp_pktin_queue_stats_t *s)
+{
+	if (!e || !s || idx < 0 || (uint32_t)idx >= (e->num_in ? e->num_in : 1u))
+		return -1;
+	memset(s, 0, sizeof(*s));
+	s->octets = odp_atomic_load_u64(&e->inq_st[idx].octets);
+	s->packets = odp_atomic_load_u64(&e->inq_st[idx].packets);
+	s->discards = odp_atomic_load_u64(&e->inq_st[idx].discards);
+	s->errors = odp_atomic_load_u64(&e->inq_st[idx].errors);
+	return 0;
+}
+
+int odp_pktin_queue_stats(odp_pktin_queue_t q, odp_pktin_queue_stats_t *s)
+{
+	rt_pktio_t *e = get_pk(q.pktio);
+
+	if (!e || e->param.in_mode != ODP_PKTIN_MODE_DIRECT)
+		return -1;
+	return pktin_stats_of(e, q.index, s);
+}
+
+int odp_pktin_event_queue_stats(odp_pktio_t h, odp_queue_t queue, odp_pktin_queue_stats_t *s)
+{
+	rt_pktio_t *e = get_pk(h);
+
+	if (!e || queue == ODP_QUEUE_INVALID ||
+	    (e->param.in_mode != ODP_PKTIN_MODE_SCHED && e->param.in_mode != ODP_PKTIN_MODE_QUEUE))
+		return -1;
+	for (int i = 0; i < ODP_PKTIN_MAX_QUEUES; i++)
+		if (e->inq[i] == queue)
+			return pktin_stats_of(e, i, s);
+	return -1;
+}
+
+int odp_pktout_queue_stats(odp_pktout_queue_t q, odp_pktout_queue_stats_t *s)
+{
+	rt_pktio_t *e = get_pk(q.pktio);
+
+	if (!e || !s || e->param.out_mode != ODP_PKTOUT_MODE_DIRECT || q.index < 0 ||
+	    (uint32_t)q.index >= (e->num_out ? e->num_out : 1u))
+		return -1;
+	memset(s, 0, sizeof(*s));
+	s->octets = odp_atomic_load_u64(&e->outq_st[q.index].octets);
+	s->packets = odp_atomic_load_u64(&e->outq_st[q.index].packets);
 	return 0;
 }
 
@@ -4045,6 +4308,20 @@ int odp_amd_pktio_tx_stats(odp_pktio_t h, uint64_t *bursts, uint64_t *bounced)
 	return 0;
 }
 
+/* Build extension: of those send calls, the ones whose launch also computed
+ * the pktin flow hash (several hashed input queues). */
+int odp_amd_pktio_txq_stats(odp_pktio_t h, uint64_t *hashed)
+{
+	rt_pktio_t *e = get_pk(h);
+
+	if (!e || !hashed)
+		return -1;
+	pthread_mutex_lock(&e->txl);
+	*hashed = e->txq_bursts;
+	pthread_mutex_unlock(&e->txl);
+	return 0;
+}
+
 /* Build extension: 1 when the driver has no more input and no receive burst
  * is in flight (pcap past EOF, loop queue empty); 0 otherwise; -1 bad handle. */
 int odp_amd_pktio_rx_idle(odp_pktio_t h)
@@ -4059,14 +4336,12 @@ int odp_amd_pktio_rx_idle(odp_pktio_t h)
 	for (int k = 0; k < RX_SETS; k++)
 		if (e->rs[k].pending || e->rs[k].delivering)
 			idle = 0;
-	if (!idle)
-		;
-	else if (e->drv == DRV_PCAP)
+	if (idle && e->drv == DRV_PCAP) {
 		idle = e->eof || e->nframes == 0 || (e->next >= e->nframes && e->loops == 1);
-	else if (e->drv == DRV_LOOP)
-		idle = ((rt_queue_t *)(void *)e->loopq)->count == 0;
-	else
-		idle = 1;
+	} else if (idle && e->drv == DRV_LOOP) {
+		for (uint32_t i = 0; i < ODP_PKTIN_MAX_QUEUES && e->loopq[i] != ODP_QUEUE_INVALID; i++)
+			idle &= ((rt_queue_t *)(void *)e->loopq[i])->count == 0;
+	}
 	odp_spinlock_unlock(&e->rxl);
 	return idle;
 }

@@ -14,6 +14,7 @@
 #define RT_MAX_POOLS   64
 #define RT_MAX_QUEUES  1024
 #define RT_MAX_PKTIO   64
+#define RT_LOOP_MAX_QUEUE_SIZE 1024   /* LOOP_MAX_QUEUE_SIZE, pktio/loop.c:46 */
 #define RT_MAX_AGGR    4
 /* CONFIG_PACKET_HEADROOM (platform/linux-generic/include/odp_config_internal.h:105) */
 /* odp_pktin_config_opt_t bits the receive path implements: ipv4/udp/tcp/
@@ -140,6 +141,9 @@ struct rt_queue {
 	uint64_t cur_t0;
 	/* plain pktin queue (ODP_PKTIN_MODE_QUEUE): pktio to poll when empty */
 	int pktin_idx;          /* pktio index + 1, 0 none */
+	/* a loop pktio's loop queue of a configured size: events it holds at
+	 * most (0: no bound, every other queue) */
+	uint32_t limit;
 };
 
 /* runtime-private entry points */

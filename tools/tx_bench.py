@@ -12,7 +12,14 @@ bytes + 14 B of descriptors per packet for (a), + 22 B of descriptor and
 record for (b)) and their fraction of 8 TB/s.  --loop also measures the
 loop pktio's send rate (tests/_bin/tx_driver) with and without insertion.
 
+--hash times, interleaved in one process on a 4096-packet batch of the same
+traffic, the transmit kernel's three instantiations (checksums alone -- the
+kernel of mi_cls_chksum_insert --, checksums with the pktin flow hash, the
+hash alone), and --queues N the wall time of an odp_pktout_send call on a
+loop pktio with N hashed input queues against one (tests/_bin/mq_driver).
+
   python tools/tx_bench.py [--n 1000000] [--rounds 7] [--steps 200] [--loop] [--out FILE]
+  python tools/tx_bench.py --hash [--queues 4] [--out FILE]
 """
 import argparse
 import json
@@ -133,6 +140,96 @@ def loop_rate(a):
     return out
 
 
+def hash_kernels(a):
+    """Back-to-back launches between two device events (so a launch's time
+    includes what the queue adds between kernels), the three instantiations
+    alternating inside every round."""
+    import torch
+
+    from odp_amd import _build
+    from odp_amd import rules as R
+    from odp_amd.cls import TX_DESC_DTYPE, TxContext
+    _build.build()
+    if not torch.cuda.is_available():
+        raise SystemExit("tx_bench: no GPU")
+    n = 4096
+    b, _ = R.config3(n)
+    desc = np.zeros(b.n, TX_DESC_DTYPE)
+    desc["l3"], desc["l4"] = 14, 34
+    proto = b.buf[b.off.astype(np.int64) + 23]
+    desc["flags"] = 0x40 | np.where(proto == 17, 0x10, np.where(proto == 6, 0x20, 0)).astype(np.uint8)
+    dev = torch.device("cuda:0")
+    t = TxContext(0)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ck, both, alone, keep = [], [], [], []
+    for _ in range(a.rotate):
+        tb = torch.from_numpy(b.buf).to(dev)
+        to = torch.from_numpy(b.off.astype(np.uint32).view(np.int32)).to(dev)
+        tl = torch.from_numpy(b.len.astype(np.uint16).view(np.int16)).to(dev)
+        td = torch.from_numpy(desc.view(np.int64).copy()).to(dev)
+        tdone = torch.zeros(b.n, dtype=torch.uint8, device=dev)
+        th = torch.zeros(b.n, dtype=torch.int32, device=dev)
+        keep += [tb, to, tl, td, tdone, th]
+        p = (tb.data_ptr(), to.data_ptr(), tl.data_ptr(), td.data_ptr(), b.n, 0xF0, tdone.data_ptr())
+        ck.append(p + (stream,))
+        both.append(p + (63, th.data_ptr(), True, stream))
+        alone.append(p + (63, th.data_ptr(), False, stream))
+    cur = torch.cuda.current_stream(dev)
+    variants = (("chksum", t.insert_device, ck), ("chksum_hash", t.hash_device, both),
+                ("hash", t.hash_device, alone))
+    for _, fn, args in variants:
+        span_ms(torch, cur, 50 * a.rotate, fn, args)
+    ms = {k: [] for k, _, _ in variants}
+    steps = max(a.steps, 2000)
+    for _ in range(a.rounds):
+        for k, fn, args in variants:
+            ms[k].append(span_ms(torch, cur, steps, fn, args))
+    from tests import txq_model as TQ
+    exp, _ = TQ.apply(b.buf, b.off, b.len, desc, 63)
+    same = bool(np.array_equal(keep[5].cpu().numpy().view(np.uint32), exp))
+    t.close()
+    res = {"packets": b.n, "frame_bytes": int(b.len.astype(np.int64).sum()), "steps": steps, "rounds": a.rounds,
+           "hash_equals_model": same}
+    for k in ms:
+        res[k] = {"us_per_launch_median": round(1e3 * statistics.median(ms[k]), 3),
+                  "us_per_launch_min": round(1e3 * min(ms[k]), 3),
+                  "rounds_us": [round(1e3 * x, 3) for x in ms[k]]}
+    res["chksum_hash_over_chksum_median"] = round(
+        res["chksum_hash"]["us_per_launch_median"] / res["chksum"]["us_per_launch_median"], 4)
+    return res
+
+
+def queue_send(a):
+    """Wall time of an odp_pktout_send call (256 packets) on a loop pktio:
+    one input queue against a.queues hashed ones, with and without pktout
+    checksums, alternating."""
+    import tempfile
+
+    from odp_amd import rules as R
+    from tests.rt_helpers import write_pcap
+    b, _ = R.config3(a.loop_frames)
+    drv = os.path.join(ROOT, "tests", "_bin", "mq_driver")
+    keys = [(f"q{nq}_{'chksum' if bits != '0x0' else 'plain'}", nq, bits)
+            for bits in ("0x0", "0xF0") for nq in (1, a.queues)]
+    out = {"frames": b.n, "burst": 256, "queues": a.queues, "us_per_send_call": {k: [] for k, _, _ in keys},
+           "launches": {}}
+    with tempfile.TemporaryDirectory() as d:
+        pcap = os.path.join(d, "imix.pcap")
+        write_pcap(pcap, [b.frame(i) for i in range(b.n)])
+        env = dict(os.environ, TX_COUNT_ONLY="1", TX_POOL_NUM=str(b.n + 1024), MQ_BURST="256")
+        for _ in range(3):
+            for key, nq, bits in keys:
+                r = subprocess.run([drv, "loop", pcap, "direct", str(nq), "0x3f", "1", bits, "0"],
+                                   stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120,
+                                   env=env)
+                if r.returncode:
+                    raise RuntimeError(f"mq_driver rc={r.returncode}: {r.stderr[-500:]}")
+                w = [ln.split() for ln in r.stdout.splitlines() if ln.startswith("R ")][0]
+                out["us_per_send_call"][key].append(round(int(w[3]) / int(w[2]) / 1e3, 2))
+                out["launches"][key] = [ln.split()[1:] for ln in r.stdout.splitlines() if ln.startswith("T ")][0]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -141,8 +238,18 @@ def main():
     ap.add_argument("--rotate", type=int, default=4)
     ap.add_argument("--loop", action="store_true")
     ap.add_argument("--loop-frames", type=int, default=16384)
+    ap.add_argument("--hash", action="store_true")
+    ap.add_argument("--queues", type=int, default=4)
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.hash:
+        res = {"kernels_4096": hash_kernels(a), "send_call": queue_send(a)}
+        s = json.dumps(res)
+        print(s, flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(s + "\n")
+        return
     res = kernels(a)
 
     def emit():
