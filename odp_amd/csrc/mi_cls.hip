@@ -555,6 +555,8 @@ extern "C" int mi_cls_classify(mi_cls_ctx_t *c, const uint8_t *pkts, const uint3
 	if (a.seq == 0u)   // wrapped: the hint word may equal seq - 1 by accident
 		a.seq = c->seq = 2u;
 	memcpy(a.stats_mask, c->stats_mask, sizeof(a.stats_mask));
+	// the program's header words (the loaded program's host copy: what d_dev holds)
+	memcpy(a.hdr, c->prog.w.data(), sizeof(a.hdr));
 	const Shape sh = pick_shape(c, c->opt);
 	const int nw = sh.nw;
 	const bool lt = sh.lt;

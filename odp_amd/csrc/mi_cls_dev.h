@@ -480,7 +480,8 @@ struct Crc32cTab {
 		}
 	}
 };
-static __constant__ Crc32cTab c_crc32c;
+// (16-B aligned: mi_cls_kernel copies it to LDS in 16-B pieces)
+static __constant__ __attribute__((aligned(16))) Crc32cTab c_crc32c;
 
 // Table lookups go to the kernel's LDS copy of c_crc32c (`tab`, 4 x 256
 // words): a lane walks its own frame, so the lookups are divergent.
@@ -1990,6 +1991,11 @@ struct KArgs {
 	// performance hint -- results never depend on it.
 	uint32_t *hint;
 	uint32_t seq;
+	// the device program's header words dev[0 .. DH_WORDS) (DH_*), from the
+	// host's copy of the program: the kernel takes the default / error CoS,
+	// the hot region's place and size and the predictor's ends from its
+	// arguments, so nothing at block start waits for a read of dev[]
+	uint32_t hdr[DH_WORDS];
 };
 
 __device__ __forceinline__ bool stats_bit(const KArgs &a, uint32_t c)
@@ -2168,26 +2174,81 @@ __global__ __launch_bounds__(NW * WAVE, waves_per_eu(NW)) void mi_cls_kernel(KAr
 	__shared__ uint32_t s_l4[256];
 	__shared__ uint32_t s_next;   // the block's tile counter (dynamic tiles)
 	// CRC-32C slicing tables and piece shifts (pktin options)
-	__shared__ uint32_t s_crc[CK ? CRC_WORDS : 1];
+	__shared__ __attribute__((aligned(CK ? 16 : 4))) uint32_t s_crc[CK ? CRC_WORDS : 1];
 
 	const uint32_t lane = threadIdx.x & (WAVE - 1);
 	const uint32_t wave = threadIdx.x >> 6;
 	uint32_t *W = s_win + wave * RS * WROWS;
 
+	// Block setup.  Nothing in it waits for anything else in it: the header
+	// words of the device program come with the kernel arguments (KArgs.hdr),
+	// the hot region, the CRC tables and the L4 table depend on arguments
+	// alone.  So the setup loads are issued first, back to back as one batch
+	// per thread, then the first descriptors; the batch is written to LDS
+	// (older than the descriptors in the in-order vmcnt queue, it has landed
+	// by the time they have), the first tile's window loads are issued, and
+	// the barrier below is reached while they are in flight: no wait for
+	// setup data waits for a window load, and no wave waits at the barrier
+	// for another wave's windows.
 	const cword_t dev = (cword_t)a.dev;
-	const int32_t def_cos = (int32_t)dev[DH_DEFAULT];
-	const int32_t err_cos = (int32_t)dev[DH_ERROR];
-	const uint32_t def_valid = dev[DH_DEFAULT_VALID];
-	const uint32_t max_hops = dev[DH_MAX_HOPS];
-	const uint32_t hot_off = dev[DH_HOT_OFF];
+	const int32_t def_cos = (int32_t)a.hdr[DH_DEFAULT];
+	const int32_t err_cos = (int32_t)a.hdr[DH_ERROR];
+	const uint32_t def_valid = a.hdr[DH_DEFAULT_VALID];
+	const uint32_t max_hops = a.hdr[DH_MAX_HOPS];
+	const uint32_t hot_off = a.hdr[DH_HOT_OFF];
+	constexpr uint32_t NT = NW * WAVE;
+	// Hot region -> LDS in 16-B pieces (the device program and the dynamic
+	// LDS size are padded to 16 B), SETUP_HOT pieces per thread in the batch:
+	// what the largest region a shape accepts takes -- the CU's 160 KiB less
+	// the block's windows in the one-block-per-CU shapes (4 pieces per thread
+	// for 16 waves, 7 for 12, 14 for 8: waves with that many registers to
+	// spare), the 20-KB default cap of 4-wave blocks (5).  Buffer loads: a
+	// piece past the region reads as zero without a branch or a memory access.
+	// (tests/test_gpu_block_setup.py restates this formula for its cases at
+	// the bounds: a change here belongs there too.)
+	constexpr uint32_t SETUP_HOT =
+		NW == 4 ? 5u : (160u * 1024u - (uint32_t)sizeof(s_win)) / 16u / NT + 1u;
+	static_assert(SETUP_HOT <= 14u, "the batch lives in registers");
+	const uint32_t hq = LT ? (a.hdr[DH_HOT_WORDS] + 3u) >> 2 : 0u;
+	const __amdgpu_buffer_rsrc_t hot_rs = __builtin_amdgcn_make_buffer_rsrc(
+		(void *)(a.dev + hot_off), (short)0, (int)(hq * 16u), 0x00020000);
+	u32x4 hot_p[LT ? SETUP_HOT : 1];
+	if constexpr (LT) {
+#pragma unroll
+		for (uint32_t j = 0; j < SETUP_HOT; ++j)
+			hot_p[j] = __builtin_amdgcn_raw_buffer_load_b128(hot_rs, (threadIdx.x + j * NT) * 16u, 0, 0);
+	}
+	// CRC-32C tables (pktin options): Crc32cTab's words in order (CRC_*
+	// offsets), whole 16-B pieces in the batch and the last word on its own
+	constexpr uint32_t CRC_Q = CRC_WORDS / 4u;
+	constexpr uint32_t SETUP_CRC = CK ? (CRC_Q + NT - 1u) / NT : 1u;
+	static_assert(CRC_Q * 4u + 1u == CRC_WORDS, "one word past the 16-B pieces");
+	u32x4 crc_p[SETUP_CRC];
+	uint32_t crc_last = 0;
+	if constexpr (CK) {
+		const __amdgpu_buffer_rsrc_t crc_rs = __builtin_amdgcn_make_buffer_rsrc(
+			(void *)&c_crc32c, (short)0, (int)(CRC_Q * 16u), 0x00020000);
+#pragma unroll
+		for (uint32_t j = 0; j < SETUP_CRC; ++j)
+			crc_p[j] = __builtin_amdgcn_raw_buffer_load_b128(crc_rs, (threadIdx.x + j * NT) * 16u, 0, 0);
+		crc_last = reinterpret_cast<const uint32_t *>(&c_crc32c)[CRC_WORDS - 1u];   // a scalar load
+	}
+	// L4 protocol table: a word per thread, in the batch too (built from
+	// immediates -- selects over its 8 non-zero entries per thread -- it
+	// needs no load, but the 16-wave option kernels then spill more: 16 / 80 B
+	// of scratch for 12 / 72)
+	const __amdgpu_buffer_rsrc_t l4_rs = __builtin_amdgcn_make_buffer_rsrc(
+		(void *)&c_l4tab, (short)0, (int)sizeof(L4Tab), 0x00020000);
+	static_assert(NT >= 256u, "a thread per protocol number");
+	const uint32_t l4_p = __builtin_amdgcn_raw_buffer_load_b32(l4_rs, threadIdx.x * 4u, 0, 0);
 	const cword_t hc = dev + hot_off;                 // hot region, scalar reads
-	const cword_t prog = dev + dev[DH_PROG_OFF];
+	const cword_t prog = dev + a.hdr[DH_PROG_OFF];
 	// the default CoS's words (the first descent round always evaluates it)
 	const cword_t dce = hc + COS_WORDS * (uint32_t)max(def_cos, 0);
 	const uint32_t d_nr = def_cos >= 0 ? dce[C_NR] : 0u;
 	// bit 31: a chain of blocks (never set in tree programs)
 	const uint32_t d_bv = DIV ? dce[C_BV] & C_BV_OFF : dce[C_BV] & 0x7fffffffu, d_rec0 = dce[C_REC0];
-	const uint32_t j_off = DIV ? dev[DH_JOINT] : 0u;   // joint groups' directory
+	const uint32_t j_off = DIV ? a.hdr[DH_JOINT] : 0u;   // joint groups' directory
 	const bool stats_on = a.stats != nullptr;
 	typedef typename std::conditional<LT, lword_t, gword_t>::type hot_t;
 	hot_t H;
@@ -2214,7 +2275,7 @@ __global__ __launch_bounds__(NW * WAVE, waves_per_eu(NW)) void mi_cls_kernel(KAr
 		return t < nt ? t : 0xFFFFFFFFu;
 	};
 	uint32_t tile = tile_of(wave), nx = tile_of(NW + wave), nn = 0xFFFFFFFFu;
-	// first descriptors before the hot-region copy: their latency overlaps it
+	// first descriptors, behind the setup batch in the vmcnt queue
 	uint32_t d_off = 0, d_len = 0, n_off = 0, n_len = 0;
 	{
 		const uint32_t p0 = tile * WAVE + lane, p1 = nx * WAVE + lane;
@@ -2254,35 +2315,48 @@ __global__ __launch_bounds__(NW * WAVE, waves_per_eu(NW)) void mi_cls_kernel(KAr
 		want_hi = false;
 	bool saw_hi = false;
 	uint32_t d_win = WIN, my_win = WIN;
-	const uint32_t p_l3end = dev[DH_L3END], p_l4end = dev[DH_L4END], p_frend = dev[DH_FREND];
-	// the first tile's windows are in flight during the block setup below
-	if (tile < nt)
-		d_hi = load_window(rs, d_off, d_len, lane, d, want_hi, d_win);
+	const uint32_t p_l3end = a.hdr[DH_L3END], p_l4end = a.hdr[DH_L4END], p_frend = a.hdr[DH_FREND];
+	// The batch -> LDS, then the window loads.  The writes come first so that
+	// their waits stand ahead of the window loads in every wave: placed after
+	// them, the compiler's wait counts, merged with the path of a wave without
+	// a tile, drained the windows before the barrier.  The descriptors have to
+	// land before the windows are issued anyway, and they are younger than the
+	// batch.
 	if constexpr (LT) {
-		// hot region -> LDS in 16-B pieces (the device program and the
-		// dynamic LDS size are padded to 16 B)
-		const uint32_t hq = (dev[DH_HOT_WORDS] + 3u) >> 2;
-		typedef const __attribute__((address_space(1))) u32x4 *gvec_t;
-		const gvec_t src = (gvec_t)(a.dev + hot_off);
 		u32x4 *dst = (u32x4 *)s_dyn;
-		for (uint32_t i = threadIdx.x; i < hq; i += NW * WAVE)
-			dst[i] = src[i];
+#pragma unroll
+		for (uint32_t j = 0; j < SETUP_HOT; ++j) {
+			const uint32_t i = threadIdx.x + j * NT;
+			if (i < hq)
+				dst[i] = hot_p[j];
+		}
+		// a region past the batch (none of the shapes' limits allows one)
+		for (uint32_t i = threadIdx.x + SETUP_HOT * NT; i < hq; i += NT)
+			dst[i] = __builtin_amdgcn_raw_buffer_load_b128(hot_rs, i * 16u, 0, 0);
 		H = (lword_t)s_dyn;
 	} else {
 		H = (gword_t)(a.dev + hot_off);
 	}
+	if constexpr (CK) {
+		u32x4 *dst = (u32x4 *)s_crc;
+#pragma unroll
+		for (uint32_t j = 0; j < SETUP_CRC; ++j) {
+			const uint32_t i = threadIdx.x + j * NT;
+			if (i < CRC_Q)
+				dst[i] = crc_p[j];
+		}
+		if (threadIdx.x == NT - 1u)
+			s_crc[CRC_WORDS - 1u] = crc_last;
+	}
+	if (threadIdx.x < 256u)
+		s_l4[threadIdx.x] = l4_p;
+	// the first tile's windows are in flight from here, through the barrier
+	if (tile < nt)
+		d_hi = load_window(rs, d_off, d_len, lane, d, want_hi, d_win);
 
 	if (stats_on) {
 		for (uint32_t i = threadIdx.x; i < MAX_STATS_COS; i += NW * WAVE)
 			s_cnt[i] = 0;
-	}
-	for (uint32_t i = threadIdx.x; i < 256u; i += NW * WAVE)
-		s_l4[i] = c_l4tab.v[i];
-	if constexpr (CK) {
-		// Crc32cTab's words in order (CRC_* offsets)
-		const uint32_t *cw = reinterpret_cast<const uint32_t *>(&c_crc32c);
-		for (uint32_t i = threadIdx.x; i < CRC_WORDS; i += NW * WAVE)
-			s_crc[i] = cw[i];
 	}
 	for (uint32_t r = WIN / 4; r < WROWS; ++r)
 		W[r * RS + lane] = 0u;   // pad / zero rows: always zero
