@@ -809,6 +809,94 @@ typedef struct mi_cls_rxc_args {
 int mi_cls_rx_chain_submit(mi_cls_ctx_t *ctx, const uint8_t *pkts, size_t bytes,
 			   const mi_cls_rxc_args_t *args, uint64_t *ticket);
 
+/* ------------------------------------------------------------------------
+ * The enqueue plan: what a pktio driver does with a classified batch's
+ * records, one packet at a time, before its packets are on their queues
+ * (reference pktio/loop.c:311-312, 324-325, 352-355, 380-381: the counters;
+ * include/odp_classification_internal.h:208-236 _odp_cls_enq: runs of equal
+ * destination enqueued in arrival order), for a batch of any size and up to
+ * MI_CLS_ENQ_DST_MAX destination queues.  No pools, no packet handles: every
+ * enqueued record is delivered; allocation and the CoS pool switch stay with
+ * the caller.  Per record, in arrival order:
+ *   in_errors    err != 0, or outcome MI_CLS_OUT_PARSE_DROP;
+ *   in_discards  outcome MI_CLS_OUT_DISCARD or MI_CLS_OUT_LOOP;
+ *   delivered    outcome MI_CLS_OUT_ENQ whose (cos, queue) the table maps:
+ *                queue < cos_nq[cos], cos_q0[cos] + queue < MI_CLS_ENQ_ENT and
+ *                the entry's id < ndst; it goes to that destination id;
+ *   stale        outcome MI_CLS_OUT_ENQ that the table does not map (the
+ *                records are of other rules than the table): not delivered;
+ *   packets / octets  delivered records with err == 0, and their len summed.
+ * perm[n] is a permutation of 0 .. n-1: the delivered records grouped by
+ * destination id ascending, arrival order inside a group, then every record
+ * that is not delivered as one last group, in arrival order (one free call).
+ * gbeg[ndst + 2]: group g is perm[gbeg[g] .. gbeg[g+1]); group ndst is the
+ * not-delivered one; gbeg[0] == 0, gbeg[ndst + 1] == n.
+ * Multi-GPU: there is no mi_cls_group_* form.  Shards planned per device
+ * concatenate in shard order: a queue's packets of shard k precede those of
+ * shard k + 1, which is arrival order (mi_cls_shard cuts contiguous slices).
+ * ---------------------------------------------------------------------- */
+#define MI_CLS_ENQ_ENT 8192      /* (CoS, queue slot) entries: 255 CoS x 32 hash queues fit */
+#define MI_CLS_ENQ_DST_MAX 8192  /* destination ids                                          */
+/* The kernels' shape: a block of 16 waves ranks MI_CLS_ENQ_TILE records at a
+ * time and walks a contiguous run of tiles; at most MI_CLS_ENQ_GRID blocks
+ * (grid = min(MI_CLS_ENQ_GRID, tiles); a batch of more tiles gives each block
+ * ceil(tiles / grid) of them).  Destination ids are grouped in stable passes of
+ * MI_CLS_ENQ_DIGIT bits: one pass when ndst + 1 <= 1 << MI_CLS_ENQ_DIGIT, else
+ * two. */
+#define MI_CLS_ENQ_TILE 1024
+#define MI_CLS_ENQ_GRID 256
+#define MI_CLS_ENQ_DIGIT 8
+
+typedef struct mi_cls_enq_tab {
+	uint32_t ndst;                    /* destination ids in use (<= MI_CLS_ENQ_DST_MAX) */
+	uint32_t rsv;
+	uint8_t  cos_nq[256];             /* CoS index -> its queues (0: none: drop CoS,
+					   * invalid CoS)                                  */
+	uint16_t cos_q0[256];             /* its first entry of ent_dst                     */
+	uint16_t ent_dst[MI_CLS_ENQ_ENT]; /* (CoS, queue slot) -> destination id; entries
+					   * of one odp_queue_t share an id                */
+	uint64_t stamp;                   /* new value whenever the table is rewritten: the
+					   * device keeps the copy of the last stamp        */
+} mi_cls_enq_tab_t;
+
+typedef struct mi_cls_enq_out {
+	uint64_t in_errors, in_discards, packets, octets;
+	uint64_t delivered;               /* records in groups 0 .. ndst-1                  */
+	uint64_t stale;                   /* enqueue records the table does not map         */
+} mi_cls_enq_out_t;
+
+/* Plan n records in device memory.  res_dev / len_dev: the records and frame
+ * lengths (the len_dev of mi_cls_classify); perm_dev n words, gbeg_dev
+ * tab->ndst + 2 words, out_dev one mi_cls_enq_out_t (8-byte aligned): all
+ * written whole, no input value of theirs is read.  tab is host memory, read
+ * during the call.  The context needs no rules.  Stream-ordered on `stream`
+ * (after mi_cls_classify on the same stream the records never leave the
+ * device); returns after the launches are enqueued.  The scratch (11 B per
+ * record) is the context's, grown by 1.5x and kept; a call on another stream
+ * than the previous plan's is ordered after it.  n == 0: gbeg and out are
+ * zeroed (res / len / perm may be NULL).  -EINVAL: a NULL array, or a NULL
+ * context where there is a device; -ENODEV: no device; -E2BIG: tab->ndst >
+ * MI_CLS_ENQ_DST_MAX.  mi_cls_last_launch: info[0] 128 + the waves per block
+ * (144), [1] the digit passes (1, 2; 0 for n == 0), [2]-[5] 0, [6] the grid. */
+int mi_cls_enq_plan(mi_cls_ctx_t *ctx, const mi_cls_result_t *res_dev, const uint16_t *len_dev,
+		    uint32_t n, const mi_cls_enq_tab_t *tab, uint32_t *perm_dev, uint32_t *gbeg_dev,
+		    mi_cls_enq_out_t *out_dev, void *stream);
+
+/* Host-memory batch, with the semantics of mi_cls_chksum_insert_host and its
+ * submit / wait forms: res, len, perm, gbeg and out all page-locked
+ * (mi_cls_host_alloc): read and written in place; otherwise the records and
+ * lengths go through the context's staging buffers and perm, gbeg and out are
+ * copied back.  Tickets come from the context's ring (the buffers stay
+ * untouched until the wait; tab may change after the submit returns). */
+int mi_cls_enq_plan_host(mi_cls_ctx_t *ctx, const mi_cls_result_t *res_host, const uint16_t *len_host,
+			 uint32_t n, const mi_cls_enq_tab_t *tab, uint32_t *perm_host,
+			 uint32_t *gbeg_host, mi_cls_enq_out_t *out_host);
+int mi_cls_enq_plan_host_submit(mi_cls_ctx_t *ctx, const mi_cls_result_t *res_host,
+				const uint16_t *len_host, uint32_t n, const mi_cls_enq_tab_t *tab,
+				uint32_t *perm_host, uint32_t *gbeg_host, mi_cls_enq_out_t *out_host,
+				uint64_t *ticket);
+int mi_cls_enq_plan_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
+
 /* 1 if p lies in page-locked host memory that the device addresses at the
  * same address (the receive delivery's requirement), else 0. */
 int mi_cls_host_mapped(const void *p);

@@ -390,6 +390,39 @@ struct mi_cls_rxtab;
 int odp_amd_cls_rxtab_fill(odp_pool_t pktio_pool, struct mi_cls_rxtab *tab, odp_pool_t pools[],
 			   uint32_t *npool, uint64_t *gen);
 
+/* The enqueue plan's table of the current control plane (mi_cls_enq_tab_t,
+ * mi_cls.h), built on the host (no device needed): per CoS index its queues
+ * and each one's destination id.  Entries of one odp_queue_t share an id (two
+ * CoS on one queue keep one arrival order); ids count up in order of first
+ * appearance scanning CoS index, then queue slot; a CoS whose action is DROP
+ * has no entries.  queues[id] (room for MI_CLS_ENQ_DST_MAX): the queue of
+ * each id; *ndst: ids in use; *gen: the generation the table was built under
+ * (rebuild it when odp_amd_cls_generation() has moved).  0, -EINVAL, or
+ * -E2BIG when the control plane does not fit the table. */
+struct mi_cls_enq_tab;
+struct mi_cls_enq_out;
+int odp_amd_cls_enqtab_fill(struct mi_cls_enq_tab *tab, odp_queue_t queues[], uint32_t *ndst,
+			    uint64_t *gen);
+
+/* The enqueue plan of a classified batch on the pktio's context
+ * (mi_cls_enq_plan: records and lengths in device memory, on the stream of
+ * odp_amd_cls_classify the records never leave the device) and its host forms
+ * (mi_cls_enq_plan_host, _submit / _wait on the context's ticket ring): the
+ * stable grouping by destination queue (one odp_queue_enq_multi per group), the
+ * records that are not delivered as the last group (one free), the pktio
+ * counters.  -ENOTSUP on pktios over several GPUs: plan each shard on its
+ * device; the shards' groups concatenate in shard order. */
+int odp_amd_cls_enq_plan(odp_pktio_t pktio, const void *res_dev, const uint16_t *len_dev, uint32_t n,
+			 const struct mi_cls_enq_tab *tab, uint32_t *perm_dev, uint32_t *gbeg_dev,
+			 struct mi_cls_enq_out *out_dev, void *stream);
+int odp_amd_cls_enq_plan_host(odp_pktio_t pktio, const void *res, const uint16_t *len, uint32_t n,
+			      const struct mi_cls_enq_tab *tab, uint32_t *perm, uint32_t *gbeg,
+			      struct mi_cls_enq_out *out);
+int odp_amd_cls_enq_plan_host_submit(odp_pktio_t pktio, const void *res, const uint16_t *len,
+				     uint32_t n, const struct mi_cls_enq_tab *tab, uint32_t *perm,
+				     uint32_t *gbeg, struct mi_cls_enq_out *out, uint64_t *ticket);
+int odp_amd_cls_enq_plan_host_wait(odp_pktio_t pktio, uint64_t ticket);
+
 /* Device contexts of the pktio (its GPUs, ODP_AMD_GPUS / create_multi); 1
  * for a single-device pktio, < 0 on error. */
 int odp_amd_cls_devices(odp_pktio_t pktio);

@@ -102,6 +102,43 @@ class ParseParam(C.Structure):
     _fields_ = [("proto", C.c_uint32), ("last_layer", C.c_uint32), ("chksums", C.c_uint32)]
 
 
+# the enqueue plan (include/mi_cls.h): the table's bounds, the kernels' shape
+ENQ_ENT, ENQ_DST_MAX = 8192, 8192
+ENQ_TILE, ENQ_GRID, ENQ_DIGIT = 1024, 256, 8
+
+
+class EnqTab(C.Structure):
+    """mi_cls_enq_tab_t."""
+    _fields_ = [("ndst", C.c_uint32), ("rsv", C.c_uint32), ("cos_nq", C.c_uint8 * 256),
+                ("cos_q0", C.c_uint16 * 256), ("ent_dst", C.c_uint16 * ENQ_ENT), ("stamp", C.c_uint64)]
+
+
+class EnqOut(C.Structure):
+    """mi_cls_enq_out_t."""
+    _fields_ = [("in_errors", C.c_uint64), ("in_discards", C.c_uint64), ("packets", C.c_uint64),
+                ("octets", C.c_uint64), ("delivered", C.c_uint64), ("stale", C.c_uint64)]
+
+
+ENQ_OUT_FIELDS = tuple(f[0] for f in EnqOut._fields_)
+_enq_stamps = 0
+
+
+def enq_tab(cos_nq, cos_q0, ent_dst, ndst) -> EnqTab:
+    """A mi_cls_enq_tab_t from its arrays (cos_nq / cos_q0: up to 256 values
+    by CoS index, ent_dst: up to ENQ_ENT destination ids), with a stamp no
+    earlier table of this process had."""
+    global _enq_stamps
+    t = EnqTab()
+    t.ndst = int(ndst)
+    for name, src in (("cos_nq", cos_nq), ("cos_q0", cos_q0), ("ent_dst", ent_dst)):
+        a = np.ctypeslib.as_array(getattr(t, name))
+        s = np.asarray(src)
+        a[:s.shape[0]] = s
+    _enq_stamps += 1
+    t.stamp = (1 << 32) + _enq_stamps
+    return t
+
+
 # odp_proto_t, odp_proto_layer_t, odp_proto_chksums_t.all_chksum
 PROTO_ETH, PROTO_IPV4, PROTO_IPV6 = 1, 2, 3
 LAYER_L2, LAYER_L3, LAYER_L4, LAYER_ALL = 1, 2, 3, 4
@@ -186,6 +223,18 @@ def _load():
         "mi_cls_lso_segment_host_submit": (i32, [vp, vp, C.c_size_t, vp, vp, vp, u32, vp, C.c_size_t, vp,
                                                  u32, vp, u32, vp, C.POINTER(C.c_uint64)]),
         "mi_cls_lso_segment_host_wait": (i32, [vp, C.c_uint64]),
+        "mi_cls_enq_plan": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), vp, vp, vp, vp]),
+        "mi_cls_enq_plan_host": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), vp, vp, vp]),
+        "mi_cls_enq_plan_host_submit": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), vp, vp, vp,
+                                              C.POINTER(C.c_uint64)]),
+        "mi_cls_enq_plan_host_wait": (i32, [vp, C.c_uint64]),
+        "odp_amd_cls_enqtab_fill": (i32, [C.POINTER(EnqTab), C.POINTER(vp), C.POINTER(u32),
+                                          C.POINTER(C.c_uint64)]),
+        "odp_amd_cls_enq_plan": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), vp, vp, vp, vp]),
+        "odp_amd_cls_enq_plan_host": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), vp, vp, vp]),
+        "odp_amd_cls_enq_plan_host_submit": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), vp, vp, vp,
+                                                   C.POINTER(C.c_uint64)]),
+        "odp_amd_cls_enq_plan_host_wait": (i32, [vp, C.c_uint64]),
         "odp_amd_cls_parse_host": (i32, [vp, C.c_size_t, vp, vp, u32, u32, u32, u32, vp]),
         "odp_amd_cls_parse_term": (None, []),
     }
@@ -445,6 +494,77 @@ class ParseContext(_FeatureContext):
         rc = self.L.mi_cls_parse_host_wait(self.ctx, ticket)
         if rc != 0:
             raise RuntimeError(f"mi_cls_parse_host_wait: {rc}")
+
+
+def _enq_plan_device(call, handle, records, lens, tab, device, poison=0xA5A5A5A5):
+    """Upload records (rules.RESULT_DTYPE) and lens, run the device form
+    `call` (mi_cls_enq_plan / odp_amd_cls_enq_plan) on torch's current stream
+    and return (perm, gbeg, counters dict).  Every output word, and one guard
+    word past each array, holds `poison` before the launch."""
+    import torch
+    dev = torch.device(device)
+    rec = np.ascontiguousarray(records, dtype=R.RESULT_DTYPE)
+    n = int(rec.shape[0])
+    ln = np.ascontiguousarray(lens, dtype=np.uint16)
+    assert ln.shape[0] == n
+    ng = int(tab.ndst) + 2
+    t_res = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy() if n else np.zeros(16, np.uint8)).to(dev)
+    t_len = torch.from_numpy(ln.view(np.int16).copy() if n else np.zeros(1, np.int16)).to(dev)
+    t_perm = torch.from_numpy(np.full(n + 1, poison, np.uint32).view(np.int32)).to(dev)
+    t_gbeg = torch.from_numpy(np.full(ng + 1, poison, np.uint32).view(np.int32)).to(dev)
+    t_out = torch.from_numpy(np.full(2 * (len(ENQ_OUT_FIELDS) + 1), poison, np.uint32).view(np.int32)).to(dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = call(handle, t_res.data_ptr(), t_len.data_ptr(), n, C.byref(tab), t_perm.data_ptr(),
+              t_gbeg.data_ptr(), t_out.data_ptr(), stream or None)
+    if rc != 0:
+        raise RuntimeError(f"enq_plan: {rc} ({lib().mi_cls_strerror(rc).decode()})")
+    torch.cuda.synchronize(dev)
+    perm = t_perm.cpu().numpy().view(np.uint32)
+    gbeg = t_gbeg.cpu().numpy().view(np.uint32)
+    out = t_out.cpu().numpy().view(np.uint32)
+    if perm[n] != poison or gbeg[ng] != poison or out[-1] != poison or out[-2] != poison:
+        raise RuntimeError("enq_plan wrote past an output array")
+    ctr = out[:-2].view(np.uint64)
+    return perm[:n].copy(), gbeg[:ng].copy(), {k: int(v) for k, v in zip(ENQ_OUT_FIELDS, ctr)}
+
+
+def _enq_plan_host(L, prefix, handle, res, ln, tab, perm, gbeg, out, submit):
+    """The host forms of `prefix` (mi_cls_enq_plan_host / odp_amd_cls_enq_plan_host)
+    on numpy arrays: views of a PinnedArray are read and written in place,
+    other arrays go through the staging buffers.  out: 6 uint64
+    (ENQ_OUT_FIELDS).  submit: the _submit / _wait pair."""
+    n = int(res.shape[0])
+    args = (handle, res.ctypes.data if n else None, ln.ctypes.data if n else None, n, C.byref(tab),
+            perm.ctypes.data if n else None, gbeg.ctypes.data, out.ctypes.data)
+    if submit:
+        t = C.c_uint64()
+        rc = getattr(L, prefix + "_submit")(*args, C.byref(t))
+        if rc == 0:
+            rc = getattr(L, prefix + "_wait")(handle, t.value)
+    else:
+        rc = getattr(L, prefix)(*args)
+    if rc != 0:
+        raise RuntimeError(f"{prefix}: {rc}")
+
+
+class EnqContext(_FeatureContext):
+    """A device context for the enqueue plan (mi_cls_enq_plan and its host
+    entries: a classified batch's records grouped by destination queue, the
+    records that are not delivered, the pktio counters); needs no rules."""
+
+    def plan_device(self, d_res, d_len, n, tab, d_perm, d_gbeg, d_out, stream=0):
+        """On device pointers (ints), stream-ordered.  Returns the C status."""
+        return self.L.mi_cls_enq_plan(self.ctx, d_res or None, d_len or None, n, C.byref(tab),
+                                      d_perm or None, d_gbeg or None, d_out or None, stream or None)
+
+    def plan(self, records, lens, tab, poison=0xA5A5A5A5):
+        """Upload records and lens, plan; returns (perm, gbeg, counters)."""
+        return _enq_plan_device(self.L.mi_cls_enq_plan, self.ctx, records, lens, tab, f"cuda:{self.gpu}",
+                                poison)
+
+    def plan_host(self, res, ln, tab, perm, gbeg, out, submit=False):
+        """mi_cls_enq_plan_host (submit: _host_submit / _host_wait)."""
+        _enq_plan_host(self.L, "mi_cls_enq_plan_host", self.ctx, res, ln, tab, perm, gbeg, out, submit)
 
 
 # LSO (include/mi_cls.h): odp_lso_protocol_t / odp_lso_modify_t values, the
@@ -725,6 +845,35 @@ class Classifier:
         if rc != 0:
             raise RuntimeError(f"odp_amd_cls_classify_host: {rc}")
         return out[: batch.n]
+
+    def enq_table(self):
+        """The enqueue plan's table of the current control plane
+        (odp_amd_cls_enqtab_fill; host only).  Returns (EnqTab, queues, gen):
+        queues[id] the odp_queue_t of destination id, gen the generation the
+        table was built under."""
+        tab = EnqTab()
+        q = (C.c_void_p * ENQ_DST_MAX)()
+        nd, gen = C.c_uint32(), C.c_uint64()
+        rc = self.L.odp_amd_cls_enqtab_fill(C.byref(tab), q, C.byref(nd), C.byref(gen))
+        if rc != 0:
+            raise RuntimeError(f"odp_amd_cls_enqtab_fill: {rc}")
+        return tab, [_h(q[i]) for i in range(nd.value)], gen.value
+
+    def enq_plan(self, records, lens, tab=None, device="cuda:0", poison=0xA5A5A5A5):
+        """The enqueue plan of classified records (odp_amd_cls_enq_plan, on
+        the pktio's context and torch's current stream -- the stream of
+        classify()): returns (perm, gbeg, counters).  tab: enq_table()'s
+        (default: built now)."""
+        if tab is None:
+            tab = self.enq_table()[0]
+        return _enq_plan_device(self.L.odp_amd_cls_enq_plan, self.pktio, records, lens, tab, device, poison)
+
+    def enq_plan_host(self, res, ln, perm, gbeg, out, tab=None, submit=False):
+        """odp_amd_cls_enq_plan_host on numpy arrays (submit: the _submit /
+        _wait pair), as EnqContext.plan_host."""
+        if tab is None:
+            tab = self.enq_table()[0]
+        _enq_plan_host(self.L, "odp_amd_cls_enq_plan_host", self.pktio, res, ln, tab, perm, gbeg, out, submit)
 
     def cos_stats_packets(self, cos_handle):
         s = CosStats()

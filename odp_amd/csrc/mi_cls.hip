@@ -57,6 +57,17 @@ struct mi_cls_ctx {
 	uint64_t tab_stamp[8];         // and that table's stamp
 	mi_cls_rxtab_t *h_tab;         // per ticket slot: page-locked snapshot the copy reads
 	uint64_t submitted;
+	// the enqueue plan (mi_cls_enq_plan), made by its first call: the scratch
+	// per record (enq_cap of them) and of fixed size, the table's page-locked
+	// snapshot and whose copy the device holds, the last plan's end and stream
+	uint8_t *d_enq = nullptr, *d_enq_fix = nullptr;
+	size_t enq_cap = 0;
+	mi_cls_enq_tab_t *h_enq_tab = nullptr;
+	const void *enq_tab_src = nullptr;
+	uint64_t enq_tab_stamp = 0;
+	hipEvent_t enq_ev = nullptr;
+	hipStream_t enq_last = nullptr;
+	bool enq_used = false;
 	// program-specialised flat kernel for the loaded program (null: none)
 	std::shared_ptr<SpecCode> spec;
 	uint32_t batch_hint = 0; // largest batch per call (mi_cls_batch_hint), 0: unknown
@@ -144,6 +155,7 @@ static int preload_kernels(int device)
 		for (int ck = 0; ck < 2; ++ck)
 			chk(mi_cls_launch_parse(proto, ck != 0, 0, nullptr, ParseArgs{}));
 	chk(mi_cls_launch_lso(0, nullptr, LsoArgs{}));
+	chk(mi_cls_launch_enq(nullptr, EnqArgs{}, 0, true));
 	if (bad)
 		return bad;
 	done.insert(device);
@@ -229,6 +241,14 @@ extern "C" int mi_cls_ctx_destroy(mi_cls_ctx_t *c)
 		if (c->ev[i])
 			(void)hipEventDestroy(c->ev[i]);
 	}
+	if (c->enq_ev) {
+		(void)hipEventSynchronize(c->enq_ev);
+		(void)hipEventDestroy(c->enq_ev);
+	}
+	(void)hipFree(c->d_enq);
+	(void)hipFree(c->d_enq_fix);
+	if (c->h_enq_tab)
+		(void)hipHostFree(c->h_enq_tab);
 	(void)hipFree(c->d_rx);
 	if (c->h_tab)
 		(void)hipHostFree(c->h_tab);
@@ -1348,6 +1368,202 @@ extern "C" int mi_cls_parse_host_submit(mi_cls_ctx_t *c, const uint8_t *pkts, si
 }
 
 extern "C" int mi_cls_parse_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
+{
+	return feature_host_wait(c, ticket);
+}
+
+// ----------------------------------------------------------- the enqueue plan
+// The plan's scratch in the context, by the staging buffers' policy (grown by
+// 1.5x, kept): per record the key (2 B), the first pass' order and high digits
+// (4 + 1 B) and the staged form's perm (4 B); of fixed size the table's device
+// copy, the count matrix, the counters and the staged form's gbeg and out.
+#define ENQ_ALIGN(x) (((size_t)(x) + 255u) & ~(size_t)255u)
+#define ENQ_FIX_TAB 0u
+#define ENQ_FIX_MAT (ENQ_FIX_TAB + ENQ_ALIGN(sizeof(mi_cls_enq_tab_t)))
+#define ENQ_FIX_CTR (ENQ_FIX_MAT + ENQ_ALIGN(((size_t)MI_CLS_ENQ_GRID << MI_CLS_ENQ_DIGIT) * 4u))
+#define ENQ_FIX_OUT (ENQ_FIX_CTR + ENQ_ALIGN(sizeof(mi_cls_enq_out_t)))
+#define ENQ_FIX_GBEG (ENQ_FIX_OUT + ENQ_ALIGN(sizeof(mi_cls_enq_out_t)))
+#define ENQ_FIX_BYTES (ENQ_FIX_GBEG + ENQ_ALIGN(((size_t)MI_CLS_ENQ_DST_MAX + 2u) * 4u))
+
+static uint16_t *enq_key16(const mi_cls_ctx_t *c) { return (uint16_t *)c->d_enq; }
+static uint32_t *enq_tperm(const mi_cls_ctx_t *c) { return (uint32_t *)(c->d_enq + ENQ_ALIGN(2u * c->enq_cap)); }
+static uint32_t *enq_sperm(const mi_cls_ctx_t *c) { return enq_tperm(c) + ENQ_ALIGN(c->enq_cap) ; }
+static uint8_t *enq_hi8(const mi_cls_ctx_t *c) { return (uint8_t *)(enq_sperm(c) + ENQ_ALIGN(c->enq_cap)); }
+
+// Scratch for n records.  Before it is replaced, and before the table's
+// snapshot or device copy is rewritten, the previous plan has ended (enq_ev).
+static int enq_idle(mi_cls_ctx_t *c)
+{
+	if (c->enq_used)
+		HIP_OK(hipEventSynchronize(c->enq_ev));
+	return 0;
+}
+
+static int enq_scratch(mi_cls_ctx_t *c, uint32_t n)
+{
+	if (!c->d_enq_fix) {
+		if (hipEventCreateWithFlags(&c->enq_ev, hipEventDisableTiming) != hipSuccess)
+			return -EIO;
+		if (hipHostMalloc((void **)&c->h_enq_tab, sizeof(mi_cls_enq_tab_t), hipHostMallocDefault) != hipSuccess ||
+		    hipMalloc((void **)&c->d_enq_fix, ENQ_FIX_BYTES) != hipSuccess)
+			return -ENOMEM;
+	}
+	if (n > c->enq_cap) {
+		const int rc = enq_idle(c);
+		if (rc)
+			return rc;
+		(void)hipFree(c->d_enq);
+		c->d_enq = nullptr;
+		c->enq_cap = 0;
+		const size_t cap = n < 4096u ? 4096u : (size_t)n + n / 2;
+		if (hipMalloc((void **)&c->d_enq, ENQ_ALIGN(2u * cap) + 8u * ENQ_ALIGN(cap) + ENQ_ALIGN(cap)) != hipSuccess)
+			return -ENOMEM;
+		c->enq_cap = cap;
+	}
+	return 0;
+}
+
+// The context and the table first, then the batch
+static int enq_check(const mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len, uint32_t n,
+		     const mi_cls_enq_tab_t *tab, const uint32_t *perm, const uint32_t *gbeg,
+		     const mi_cls_enq_out_t *out)
+{
+	if (!tab)
+		return -EINVAL;
+	if (tab->ndst > MI_CLS_ENQ_DST_MAX)
+		return -E2BIG;
+	if (!c)
+		return no_ctx();
+	if (!gbeg || !out || ((uintptr_t)out & 7u) != 0)
+		return -EINVAL;
+	return n == 0 || (res && len && perm) ? 0 : -EINVAL;
+}
+
+extern "C" int mi_cls_enq_plan(mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len, uint32_t n,
+			       const mi_cls_enq_tab_t *tab, uint32_t *perm, uint32_t *gbeg,
+			       mi_cls_enq_out_t *out, void *stream)
+{
+	int rc = enq_check(c, res, len, n, tab, perm, gbeg, out);
+	if (rc)
+		return rc;
+	hipStream_t st = (hipStream_t)stream;
+	HIP_OK(set_device(c->device));
+	rc = enq_scratch(c, n);
+	if (rc)
+		return rc;
+	// the scratch is one plan's at a time: a plan on another stream follows
+	// the previous one
+	if (c->enq_used && c->enq_last != st)
+		HIP_OK(hipStreamWaitEvent(st, c->enq_ev, 0));
+	// the table's device copy, refreshed when the host table's stamp moved
+	mi_cls_enq_tab_t *dtab = (mi_cls_enq_tab_t *)(c->d_enq_fix + ENQ_FIX_TAB);
+	if (!c->enq_tab_src || c->enq_tab_src != tab || c->enq_tab_stamp != tab->stamp) {
+		rc = enq_idle(c);
+		if (rc)
+			return rc;
+		memcpy(c->h_enq_tab, tab, sizeof(*tab));
+		c->enq_tab_src = nullptr;
+		HIP_OK(hipMemcpyAsync(dtab, c->h_enq_tab, sizeof(*tab), hipMemcpyHostToDevice, st));
+		c->enq_tab_src = tab;
+		c->enq_tab_stamp = c->h_enq_tab->stamp;
+	}
+	EnqArgs a;
+	memset(&a, 0, sizeof(a));
+	a.res = res;
+	a.len = len;
+	a.tab = dtab;
+	a.n = n;
+	a.ndst = tab->ndst;
+	const uint64_t tiles = ((uint64_t)n + MI_CLS_ENQ_TILE - 1u) / MI_CLS_ENQ_TILE;
+	a.grid = (uint32_t)(tiles < MI_CLS_ENQ_GRID ? tiles : MI_CLS_ENQ_GRID);
+	a.tpb = a.grid ? (uint32_t)((tiles + a.grid - 1u) / a.grid) : 0u;
+	a.key16 = enq_key16(c);
+	a.hi8 = enq_hi8(c);
+	a.tperm = enq_tperm(c);
+	a.mat = (uint32_t *)(c->d_enq_fix + ENQ_FIX_MAT);
+	a.ctr = (unsigned long long *)(c->d_enq_fix + ENQ_FIX_CTR);
+	a.perm = perm;
+	a.gbeg = gbeg;
+	a.out = out;
+	// keys 0 .. ndst: one stable pass when they have one digit
+	const int passes = n == 0 ? 0 : a.ndst + 1u <= (1u << MI_CLS_ENQ_DIGIT) ? 1 : 2;
+	a.passes = (uint32_t)passes;
+	// this call's counters start from zero, whatever the last one left
+	HIP_OK(hipMemsetAsync(a.ctr, 0, sizeof(mi_cls_enq_out_t), st));
+	uint32_t *last = c->last;
+	last[0] = 128u + MI_CLS_ENQ_TILE / WAVE;
+	last[1] = (uint32_t)passes;
+	last[2] = last[3] = last[4] = last[5] = 0;
+	last[6] = a.grid;
+	rc = mi_cls_launch_enq(st, a, passes, false);
+	if (rc)
+		return rc;
+	HIP_OK(hipEventRecord(c->enq_ev, st));
+	c->enq_used = true;
+	c->enq_last = st;
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+// A host batch on the context's stream, nothing waited for: in place when
+// every array is page-locked, else the records and lengths through the
+// staging buffers and perm, gbeg and out through the scratch.
+static int enq_host_launch(mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len, uint32_t n,
+			   const mi_cls_enq_tab_t *tab, uint32_t *perm, uint32_t *gbeg, mi_cls_enq_out_t *out)
+{
+	HIP_OK(set_device(c->device));
+	const mi_cls_result_t *zr = res;
+	const uint16_t *zl = len;
+	uint32_t *zp = perm, *zg = gbeg;
+	mi_cls_enq_out_t *zo = out;
+	if (dev_views(zr, zl, zp, zg, zo))
+		return mi_cls_enq_plan(c, zr, zl, n, tab, zp, zg, zo, c->stream);
+	int rc = stage_bufs(c, 0, n);
+	if (!rc)
+		rc = enq_scratch(c, n);
+	if (rc)
+		return rc;
+	if (n) {
+		HIP_OK(hipMemcpyAsync(c->d_out, res, n * sizeof(mi_cls_result_t), hipMemcpyHostToDevice, c->stream));
+		HIP_OK(hipMemcpyAsync(c->d_len, len, n * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+	}
+	uint32_t *dg = (uint32_t *)(c->d_enq_fix + ENQ_FIX_GBEG);
+	mi_cls_enq_out_t *dout = (mi_cls_enq_out_t *)(c->d_enq_fix + ENQ_FIX_OUT);
+	rc = mi_cls_enq_plan(c, c->d_out, c->d_len, n, tab, enq_sperm(c), dg, dout, c->stream);
+	if (rc)
+		return rc;
+	if (n)
+		HIP_OK(hipMemcpyAsync(perm, enq_sperm(c), n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	HIP_OK(hipMemcpyAsync(gbeg, dg, ((size_t)tab->ndst + 2u) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	HIP_OK(hipMemcpyAsync(out, dout, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+	// the scratch is this plan's until the copies have read it
+	HIP_OK(hipEventRecord(c->enq_ev, c->stream));
+	return 0;
+}
+
+extern "C" int mi_cls_enq_plan_host(mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len,
+				    uint32_t n, const mi_cls_enq_tab_t *tab, uint32_t *perm, uint32_t *gbeg,
+				    mi_cls_enq_out_t *out)
+{
+	const int rc = enq_check(c, res, len, n, tab, perm, gbeg, out);
+	if (rc)
+		return rc;
+	return host_run(c, nullptr, [&] { return enq_host_launch(c, res, len, n, tab, perm, gbeg, out); });
+}
+
+extern "C" int mi_cls_enq_plan_host_submit(mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len,
+					   uint32_t n, const mi_cls_enq_tab_t *tab, uint32_t *perm,
+					   uint32_t *gbeg, mi_cls_enq_out_t *out, uint64_t *ticket)
+{
+	if (!ticket)
+		return -EINVAL;
+	*ticket = 0;
+	const int rc = enq_check(c, res, len, n, tab, perm, gbeg, out);
+	if (rc)
+		return rc;
+	return host_run(c, ticket, [&] { return enq_host_launch(c, res, len, n, tab, perm, gbeg, out); });
+}
+
+extern "C" int mi_cls_enq_plan_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
 {
 	return feature_host_wait(c, ticket);
 }

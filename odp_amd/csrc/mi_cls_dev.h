@@ -2899,6 +2899,31 @@ struct LsoArgs {
 #define LSO_NW 4            // waves per block
 int mi_cls_launch_lso(unsigned grid, hipStream_t st, const LsoArgs &a);
 
+// the enqueue plan (mi_cls_enq_plan; kernels: mi_cls_enq_dev.h, mi_cls_kq.hip)
+struct EnqArgs {
+	const mi_cls_result_t *res;
+	const uint16_t *len;
+	const mi_cls_enq_tab_t *tab;   // the device copy
+	uint32_t n;
+	uint32_t ndst;
+	uint32_t grid;                 // blocks of the key / count / scatter launches
+	uint32_t tpb;                  // tiles per block
+	uint32_t passes;               // digit passes: 1, 2 (0: n == 0)
+	uint32_t rsv;
+	uint16_t *key16;              // scratch: n keys
+	uint8_t *hi8;                  // scratch: the high digits in the first pass' order
+	uint32_t *tperm;               // scratch: the first pass' order (two passes)
+	uint32_t *mat;                 // scratch: 2^MI_CLS_ENQ_DIGIT x grid counts / starts
+	unsigned long long *ctr;       // scratch: the counters, zeroed before the launches
+	uint32_t *perm;
+	uint32_t *gbeg;
+	mi_cls_enq_out_t *out;
+};
+// The plan's launches on `st`, in order: key, scan, scatter (passes == 2:
+// count, scan, scatter again), gbeg; n == 0: gbeg alone.  preload: resolve
+// the kernels only.
+int mi_cls_launch_enq(hipStream_t st, const EnqArgs &a, int passes, bool preload);
+
 // Every launcher goes through mi_launch.  grid == 0 launches nothing: it
 // resolves the instantiation on the current device (hipFuncGetAttributes
 // loads the code object that holds it), so mi_cls_ctx_create can load every

@@ -21,6 +21,7 @@
 // builds the permutation.  HBM is not involved: every byte moves over the
 // host link, so the kernel's bound is the link, not the chip.
 #include "mi_cls_dev.h"
+#include "mi_cls_rank_dev.h"
 
 struct DArgs {
 	const uint8_t *base;
@@ -247,19 +248,7 @@ int mi_cls_launch_deliver(unsigned grid, hipStream_t st, const mi_cls_dlv_args_t
 // The classifier is on, so the parser layer is ALL (odp_packet_io.c:
 // 675-677): records need no layer cut.
 #define RXD_THREADS 1024
-
-// The lanes of the wave whose value equals this lane's (values below 2^bits):
-// one ballot per bit, no loop over the distinct values.
-__device__ __forceinline__ unsigned long long match_lanes(uint32_t v, int bits)
-{
-	unsigned long long m = ~0ull;
-	for (int b = 0; b < bits; ++b) {
-		const bool x = ((v >> b) & 1u) != 0u;
-		const unsigned long long bb = __ballot(x);
-		m &= x ? bb : ~bb;
-	}
-	return m;
-}
+// (match_lanes, the wave step of the ranks below: mi_cls_rank_dev.h)
 #define RXD_WAVES (RXD_THREADS / WAVE)
 
 // Decisions of frames [0, n) in arrival order: fate, pool slot, the frame's

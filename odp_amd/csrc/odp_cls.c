@@ -1377,6 +1377,132 @@ int odp_amd_cls_rxtab_fill(odp_pool_t pktio_pool, struct mi_cls_rxtab *tab, odp_
 	return rc;
 }
 
+/* The enqueue plan's table (mi_cls_enq_tab_t, mi_cls.h) of the current
+ * control plane: per CoS index its queues (get_dest_queue, :395-405) and each
+ * one's destination id, equal for entries of one odp_queue_t, numbered in
+ * order of first appearance scanning CoS index, then queue slot.  A CoS whose
+ * action is DROP has no entries.  queues[] (room for MI_CLS_ENQ_DST_MAX):
+ * the queue of each id; *ndst: ids in use; *gen: the generation the table
+ * reflects.  Needs no device.  -E2BIG when the control plane does not fit. */
+int odp_amd_cls_enqtab_fill(struct mi_cls_enq_tab *tab, odp_queue_t queues[], uint32_t *ndst,
+			    uint64_t *gen)
+{
+	static uint64_t stamps;   /* under G.lock */
+	enum { HT = 4 * MI_CLS_ENQ_DST_MAX };
+	uint16_t *ht;   /* open addressing: id + 1 of a queue handle */
+	uint32_t ne = 0, nd = 0;
+	int rc = 0;
+
+	if (!tab || !queues || !ndst || !gen)
+		return -EINVAL;
+	ht = calloc(HT, sizeof(*ht));
+	if (!ht)
+		return -ENOMEM;
+	memset(tab, 0, sizeof(*tab));
+	pthread_mutex_lock(&G.lock);
+	*gen = G.gen;
+	for (uint32_t i = 0; G.init && i < G.max_cos && i < 256 && rc == 0; i++) {
+		const cos_t *c = &G.cos[i];
+
+		if (!c->valid || c->action != ODP_COS_ACTION_ENQUEUE)
+			continue;
+		const uint32_t n = c->queue_group ? c->num_queue : 1u;
+
+		if (n > 255u || ne + n > MI_CLS_ENQ_ENT) {
+			rc = -E2BIG;
+			break;
+		}
+		tab->cos_nq[i] = (uint8_t)n;
+		tab->cos_q0[i] = (uint16_t)ne;
+		for (uint32_t j = 0; j < n && rc == 0; j++) {
+			const odp_queue_t q = c->queue_group ? c->hq[j] : c->queue;
+			uint32_t s = (uint32_t)(((uint64_t)(uintptr_t)q * 0x9E3779B97F4A7C15ull) >> 40) % HT;
+
+			while (ht[s] && queues[ht[s] - 1u] != q)
+				s = (s + 1u) % HT;
+			if (!ht[s]) {
+				if (nd == MI_CLS_ENQ_DST_MAX) {
+					rc = -E2BIG;
+					break;
+				}
+				queues[nd++] = q;
+				ht[s] = (uint16_t)nd;
+			}
+			tab->ent_dst[ne + j] = (uint16_t)(ht[s] - 1u);
+		}
+		ne += n;
+	}
+	/* a value no earlier table of this process had: the device copy follows it */
+	tab->stamp = ++stamps;
+	pthread_mutex_unlock(&G.lock);
+	free(ht);
+	tab->ndst = nd;
+	*ndst = nd;
+	return rc;
+}
+
+/* The plan of a classified batch on the pktio's context (mi_cls_enq_plan and
+ * its host forms; the rules take no part).  -ENOTSUP for pktios over several
+ * devices: plan each shard on its device's context. */
+static int enq_ctx(odp_pktio_t h, mi_cls_ctx_t **c)
+{
+	pktio_t *e = get_pktio(h);
+	int rc;
+
+	if (!e)
+		return -EINVAL;
+	if (e->grp || e->ngpu > 1)
+		return -ENOTSUP;
+	rc = ensure_ctx(e);
+	*c = e->ctx;
+	return rc;
+}
+
+int odp_amd_cls_enq_plan(odp_pktio_t h, const void *res_dev, const uint16_t *len_dev, uint32_t n,
+			 const struct mi_cls_enq_tab *tab, uint32_t *perm_dev, uint32_t *gbeg_dev,
+			 struct mi_cls_enq_out *out_dev, void *stream)
+{
+	mi_cls_ctx_t *c;
+	const int rc = enq_ctx(h, &c);
+
+	return rc ? rc : mi_cls_enq_plan(c, (const mi_cls_result_t *)res_dev, len_dev, n, tab, perm_dev,
+					 gbeg_dev, out_dev, stream);
+}
+
+int odp_amd_cls_enq_plan_host(odp_pktio_t h, const void *res, const uint16_t *len, uint32_t n,
+			      const struct mi_cls_enq_tab *tab, uint32_t *perm, uint32_t *gbeg,
+			      struct mi_cls_enq_out *out)
+{
+	mi_cls_ctx_t *c;
+	const int rc = enq_ctx(h, &c);
+
+	return rc ? rc : mi_cls_enq_plan_host(c, (const mi_cls_result_t *)res, len, n, tab, perm, gbeg, out);
+}
+
+int odp_amd_cls_enq_plan_host_submit(odp_pktio_t h, const void *res, const uint16_t *len, uint32_t n,
+				     const struct mi_cls_enq_tab *tab, uint32_t *perm, uint32_t *gbeg,
+				     struct mi_cls_enq_out *out, uint64_t *ticket)
+{
+	mi_cls_ctx_t *c;
+	int rc;
+
+	if (!ticket)
+		return -EINVAL;
+	*ticket = 0;
+	rc = enq_ctx(h, &c);
+	return rc ? rc : mi_cls_enq_plan_host_submit(c, (const mi_cls_result_t *)res, len, n, tab, perm, gbeg,
+						     out, ticket);
+}
+
+int odp_amd_cls_enq_plan_host_wait(odp_pktio_t h, uint64_t ticket)
+{
+	pktio_t *e = get_pktio(h);
+
+	if (!e)
+		return -EINVAL;
+	return ticket && e->ctx ? mi_cls_enq_plan_host_wait(e->ctx, ticket) : ticket ? -EINVAL : 0;
+}
+
 /* One burst's receive chain (mi_cls_rx_chain_submit) on the pktio's
  * context, under the current rules.  -ENOTSUP for pktios over several
  * devices (they take the host-decided delivery). */
