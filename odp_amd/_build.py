@@ -61,13 +61,15 @@ def build(force: bool = False, out_dir: str = PKG, defines=(), src_dir: str = SR
     mi_src = os.path.join(SRC, "mi_cls.hip")
     os.makedirs(out_dir, exist_ok=True)
     mi_so = os.path.join(out_dir, "libmi_cls.so")
-    odp_srcs = [os.path.join(SRC, f) for f in ("odp_cls.c", "odp_rt.c", "odp_pktio.c")]
+    odp_srcs = [os.path.join(SRC, f) for f in ("odp_cls.c", "odp_rt.c", "odp_pktio.c", "odp_pktin.c",
+                                                "odp_pktout.c", "odp_pcap.c")]
     odp_so = os.path.join(out_dir, "libodp_cls.so")
     odph_src = os.path.join(SRC, "odph.c")
     odph_so = os.path.join(out_dir, "libodph.so")
     rt_hdrs = hdrs + [os.path.join(INC, "odp_rt.h"), os.path.join(INC, "odp_api.h"),
                       os.path.join(INC, "odp", "helper", "odph_api.h"),
-                      os.path.join(SRC, "odp_rt_internal.h"), os.path.join(SRC, "odp_txq.h")]
+                      os.path.join(SRC, "odp_rt_internal.h"), os.path.join(SRC, "odp_txq.h"),
+                      os.path.join(SRC, "odp_pktio_internal.h"), os.path.join(SRC, "odp_pcap.h")]
     built = []
     mi_hdr = os.path.join(SRC, "mi_cls_dev.h")
     prog_hdr = os.path.join(SRC, "mi_cls_prog.h")

@@ -11,7 +11,7 @@
  * (platform/linux-generic/odp_{init,shared_memory,pool,packet,queue_basic,
  * schedule_basic,event_vector,time,cpumask}.c) is the behavioural
  * reference.  Everything here is host C: the data-plane compute
- * (parse + classify) runs on the GPU behind odp_pktio.c.
+ * (parse + classify) runs on the GPU behind odp_pktin.c.
  *
  * Design notes:
  *  - packets are single-segment: one pool element holds the header, a

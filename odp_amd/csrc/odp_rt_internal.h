@@ -1,7 +1,8 @@
 /*
  * odp_rt_internal.h -- private structures shared by the runtime sources
  * (odp_rt.c: init/shm/pools/packets/events/queues/scheduler,
- *  odp_pktio.c: packet I/O drivers and the GPU receive path).
+ *  odp_pktio.c / odp_pktin.c / odp_pktout.c: packet I/O control plane,
+ *  the GPU receive path and the transmit side, odp_pktio_internal.h).
  */
 #ifndef ODP_AMD_RT_INTERNAL_H_
 #define ODP_AMD_RT_INTERNAL_H_
@@ -162,7 +163,7 @@ void rt_packet_return_raw(odp_pool_t pool, const odp_packet_t pkt[], int num);
 int rt_queue_enq_multi(rt_queue_t *q, const odp_event_t ev[], int num);
 int rt_queue_deq_multi_raw(rt_queue_t *q, odp_event_t ev[], int num);
 int rt_thread_id(void);
-/* scheduler hooks for SCHED-mode packet input (odp_pktio.c) */
+/* scheduler hooks for SCHED-mode packet input (odp_pktin.c) */
 int rt_pktio_sched_poll(void);
 int rt_pktio_poll_index(int idx);
 uint32_t rt_gpu_index(void);

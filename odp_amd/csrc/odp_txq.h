@@ -1,5 +1,5 @@
 /* odp_txq.h -- the loop pktio's choice of an input queue for every packet of
- * a send call and the split of the call into runs, host side (odp_pktio.c
+ * a send call and the split of the call into runs, host side (odp_pktout.c
  * odp_pktout_send; reference pktio/loop.c:479-530 get_dest_queue and the
  * enqueue loop of loopback_send, :554-598).  Plain C without the runtime, so
  * that a stand-alone program can exercise it (tests/rt/txq_unit.c). */

@@ -34,17 +34,43 @@ def write_pcap(path, frames, byteorder="<", nsec=False):
             f.write(fr)
 
 
-def write_pcapng(path, frames, byteorder="<"):
-    """pcapng: SHB + IDB + one EPB per frame."""
-    def block(btype, body):
-        body += bytes((-len(body)) % 4)
-        n = 12 + len(body)
-        return struct.pack(byteorder + "II", btype, n) + body + struct.pack(byteorder + "I", n)
+def pcapng_block(btype, body, byteorder="<"):
+    """One pcapng block: type, total length, the body padded to 4 bytes, the
+    length again."""
+    body += bytes((-len(body)) % 4)
+    n = 12 + len(body)
+    return struct.pack(byteorder + "II", btype, n) + body + struct.pack(byteorder + "I", n)
+
+
+def pcapng_shb(byteorder="<"):
+    return pcapng_block(0x0a0d0d0a, struct.pack(byteorder + "IHHq", 0x1a2b3c4d, 1, 0, -1), byteorder)
+
+
+def pcapng_idb(byteorder="<", link=1, snaplen=65535):
+    return pcapng_block(1, struct.pack(byteorder + "HHI", link, 0, snaplen), byteorder)
+
+
+def pcapng_packet(i, fr, byteorder="<", kind="epb", snaplen=65535, ifc=0, caplen=None):
+    """Frame fr (number i) as an enhanced ("epb", type 6), a simple ("spb",
+    type 3: the original length, then the frame cut at the interface's snap
+    length) or an obsolete ("pb", type 2) packet block.  caplen: the captured
+    length the block states instead of the true one (malformed files)."""
+    if kind == "spb":
+        return pcapng_block(3, struct.pack(byteorder + "I", len(fr) if caplen is None else caplen) +
+                            fr[:snaplen], byteorder)
+    cap = len(fr) if caplen is None else caplen
+    if kind == "pb":
+        return pcapng_block(2, struct.pack(byteorder + "HHIIII", ifc, 0, 0, i, cap, len(fr)) + fr, byteorder)
+    return pcapng_block(6, struct.pack(byteorder + "IIIII", ifc, 0, i, cap, len(fr)) + fr, byteorder)
+
+
+def write_pcapng(path, frames, byteorder="<", kind="epb", snaplen=65535):
+    """pcapng: SHB + IDB + one packet block per frame (pcapng_packet)."""
     with open(path, "wb") as f:
-        f.write(block(0x0a0d0d0a, struct.pack(byteorder + "IHHq", 0x1a2b3c4d, 1, 0, -1)))
-        f.write(block(1, struct.pack(byteorder + "HHI", 1, 0, 65535)))
+        f.write(pcapng_shb(byteorder))
+        f.write(pcapng_idb(byteorder, snaplen=snaplen))
         for i, fr in enumerate(frames):
-            f.write(block(6, struct.pack(byteorder + "IIIII", 0, 0, i, len(fr), len(fr)) + fr))
+            f.write(pcapng_packet(i, fr, byteorder, kind, snaplen))
 
 
 # ------------------------------------------------------------------ rule text

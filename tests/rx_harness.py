@@ -1,6 +1,6 @@
 """ctypes access to the receive delivery / receive chain entry points of
 libmi_cls.so for the kernel tests (test-only; the runtime reaches them
-through odp_pktio.c).
+through odp_pktin.c).
 
 An Arena is one page-locked allocation that holds everything the device
 reads or writes in a run: frames, descriptors, records, table, packet lists,
