@@ -897,6 +897,106 @@ int mi_cls_enq_plan_host_submit(mi_cls_ctx_t *ctx, const mi_cls_result_t *res_ho
 				uint64_t *ticket);
 int mi_cls_enq_plan_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
 
+/* ------------------------------------------------------------------------
+ * The run plan: the per-run form of the enqueue plan, for CoS with packet
+ * vectors or an event aggregator, whose deliveries follow the reference's
+ * runs (include/odp_classification_internal.h:83-236 _odp_cls_enq,
+ * _odp_cos_enq, _odp_cos_vector_enq) and not the queue groups.  Delivered,
+ * stale, the destination id and the six counters are those of the enqueue
+ * plan above, under the same mi_cls_enq_tab_t.  Per record i, in arrival
+ * order, with burst(i) = i / burst (burst == 0: the whole batch is one burst):
+ *   run head     a delivered record with no earlier delivered record in its
+ *                burst, or whose latest earlier delivered record of its burst
+ *                differs from it in (destination id, cos).  Records that are
+ *                not delivered end no run; a burst's end does.  Entries that
+ *                share a destination id do not break a run; the same queue
+ *                under another CoS does, and so does the same CoS with
+ *                another id;
+ *   run          a head and the delivered records up to the next head.
+ * seq[n] is a permutation of 0 .. n-1: the delivered records in arrival
+ * order, then every other record in arrival order (one free call).
+ * runs[]: the runs in arrival order, run r = seq[first .. first + count):
+ *   plain        count < 2, or the CoS's mode has no MI_CLS_RUN_VEC: one
+ *                enqueue of `count` packets -- to the queue's aggregator when
+ *                flags has MI_CLS_RUN_AGGR (the CoS's bit); nvec = 0;
+ *   vectors      otherwise: flags = MI_CLS_RUN_VEC, nvec = ceil(count /
+ *                vmax[cos]) packet vectors of the pool of vslot[cos], all of
+ *                vmax packets but the last.
+ * out: the six counters, nruns (the true number of runs, also when it exceeds
+ * run_cap), vectors (nvec summed over all nruns runs) and vec_need[s] (nvec
+ * summed over the runs of the CoS with vslot s): a driver takes each pool's
+ * vectors with one call.
+ * ---------------------------------------------------------------------- */
+#define MI_CLS_RUN_AGGR 0x1u     /* mode bit 0: the reference's vector.use_aggr     */
+#define MI_CLS_RUN_VEC 0x2u      /* mode bit 1: not vector.use_std_enq              */
+#define MI_CLS_RUN_VSLOTS 16     /* vector pools a table tells apart                */
+/* The kernels' shape: a block of 16 waves walks a contiguous run of tiles of
+ * MI_CLS_RUN_TILE records; at most MI_CLS_RUN_GRID blocks (grid = min(
+ * MI_CLS_RUN_GRID, tiles); a batch of more tiles gives each block ceil(tiles /
+ * grid) of them). */
+#define MI_CLS_RUN_TILE 1024
+#define MI_CLS_RUN_GRID 256
+
+typedef struct mi_cls_run_tab {
+	uint8_t  mode[256];               /* CoS index -> MI_CLS_RUN_AGGR | MI_CLS_RUN_VEC  */
+	uint16_t vmax[256];               /* packets per vector (>= 1 for a VEC CoS)        */
+	uint8_t  vslot[256];              /* its vector pool's slot (< MI_CLS_RUN_VSLOTS)   */
+	uint64_t stamp;                   /* as mi_cls_enq_tab_t.stamp                      */
+} mi_cls_run_tab_t;
+
+typedef struct mi_cls_run {
+	uint32_t first;                   /* index into seq                                 */
+	uint32_t count;                   /* packets (can exceed 65535)                     */
+	uint16_t dst;                     /* destination id                                 */
+	uint8_t  cos;
+	uint8_t  flags;                   /* MI_CLS_RUN_AGGR (plain run) or MI_CLS_RUN_VEC  */
+	uint32_t nvec;
+} mi_cls_run_t;
+
+typedef struct mi_cls_run_out {
+	uint64_t in_errors, in_discards, packets, octets, delivered, stale; /* mi_cls_enq_out_t */
+	uint64_t nruns;
+	uint64_t vectors;
+	uint64_t vec_need[MI_CLS_RUN_VSLOTS];
+} mi_cls_run_out_t;
+
+/* Plan the runs of n records in device memory.  res_dev / len_dev as for
+ * mi_cls_enq_plan; seq_dev n words, runs_dev run_cap entries (16-byte
+ * aligned), out_dev one mi_cls_run_out_t (8-byte aligned).  seq, runs[0 ..
+ * min(nruns, run_cap)) and out are written whole and no input value of theirs
+ * is read; nothing past runs[min(nruns, run_cap)) is touched (a truncated
+ * plan still has the true nruns: call again with room).  tab and rtab are host
+ * memory, read and checked during the call.  Stream-ordered on `stream`;
+ * returns after the launches are enqueued.  The scratch (12 B per record) is
+ * the context's, grown by 1.5x and kept; a call on another stream than the
+ * previous run plan's is ordered after it.  n == 0: out is zeroed (res / len
+ * / seq / runs may be NULL).  -EINVAL: a NULL table or array (runs may be NULL
+ * when run_cap == 0), a NULL context where there is a device, or a CoS with
+ * MI_CLS_RUN_VEC whose vmax is 0 or whose vslot is >= MI_CLS_RUN_VSLOTS;
+ * -ENODEV: no device; -E2BIG: tab->ndst > MI_CLS_ENQ_DST_MAX.
+ * mi_cls_last_launch: info[0] 192 + the waves per block (208), [1] the
+ * launches (5; 1 for n == 0), [2]-[5] 0, [6] the grid. */
+int mi_cls_enq_runs(mi_cls_ctx_t *ctx, const mi_cls_result_t *res_dev, const uint16_t *len_dev,
+		    uint32_t n, const mi_cls_enq_tab_t *tab, const mi_cls_run_tab_t *rtab, uint32_t burst,
+		    uint32_t *seq_dev, mi_cls_run_t *runs_dev, uint32_t run_cap, mi_cls_run_out_t *out_dev,
+		    void *stream);
+
+/* Host-memory batch, as mi_cls_enq_plan_host and its submit / wait forms:
+ * res, len, seq, runs and out all page-locked: read and written in place;
+ * otherwise the records and lengths go through the context's staging buffers
+ * and seq, runs and out are copied back (the run_cap entries of runs go up
+ * first, so that those past nruns come back as they were). */
+int mi_cls_enq_runs_host(mi_cls_ctx_t *ctx, const mi_cls_result_t *res_host, const uint16_t *len_host,
+			 uint32_t n, const mi_cls_enq_tab_t *tab, const mi_cls_run_tab_t *rtab,
+			 uint32_t burst, uint32_t *seq_host, mi_cls_run_t *runs_host, uint32_t run_cap,
+			 mi_cls_run_out_t *out_host);
+int mi_cls_enq_runs_host_submit(mi_cls_ctx_t *ctx, const mi_cls_result_t *res_host,
+				const uint16_t *len_host, uint32_t n, const mi_cls_enq_tab_t *tab,
+				const mi_cls_run_tab_t *rtab, uint32_t burst, uint32_t *seq_host,
+				mi_cls_run_t *runs_host, uint32_t run_cap, mi_cls_run_out_t *out_host,
+				uint64_t *ticket);
+int mi_cls_enq_runs_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
+
 /* 1 if p lies in page-locked host memory that the device addresses at the
  * same address (the receive delivery's requirement), else 0. */
 int mi_cls_host_mapped(const void *p);

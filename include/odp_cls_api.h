@@ -423,6 +423,42 @@ int odp_amd_cls_enq_plan_host_submit(odp_pktio_t pktio, const void *res, const u
 				     uint32_t *gbeg, struct mi_cls_enq_out *out, uint64_t *ticket);
 int odp_amd_cls_enq_plan_host_wait(odp_pktio_t pktio, uint64_t ticket);
 
+/* The run plan's table of the current control plane (mi_cls_run_tab_t,
+ * mi_cls.h), built on the host (no device needed) from what
+ * odp_amd_cls_cos_enq_mode reads: per CoS index MI_CLS_RUN_AGGR (use_aggr),
+ * MI_CLS_RUN_VEC (not use_std_enq), the vector size and the slot of the
+ * vector pool.  CoS with the same vector pool share a slot; slots count up in
+ * order of first appearance scanning CoS index; a CoS whose action is DROP has
+ * no mode.  vpools[slot] (room for MI_CLS_RUN_VSLOTS = 16): each slot's pool;
+ * *nslots: slots in use; *gen: the generation the table was built under.
+ * 0, -EINVAL, or -E2BIG past 16 vector pools. */
+struct mi_cls_run_tab;
+struct mi_cls_run;
+struct mi_cls_run_out;
+int odp_amd_cls_runtab_fill(struct mi_cls_run_tab *tab, odp_pool_t vpools[], uint32_t *nslots,
+			    uint64_t *gen);
+
+/* The run plan of a classified batch on the pktio's context (mi_cls_enq_runs
+ * and its host forms): the delivered records in arrival order cut into the
+ * reference's runs, each run's packet vectors, every pool's vector need, the
+ * records that are not delivered, the pktio counters -- what a driver with
+ * packet-vector or aggregator CoS needs in place of the queue groups.
+ * -ENOTSUP on pktios over several GPUs, as the enqueue plan. */
+int odp_amd_cls_enq_runs(odp_pktio_t pktio, const void *res_dev, const uint16_t *len_dev, uint32_t n,
+			 const struct mi_cls_enq_tab *tab, const struct mi_cls_run_tab *rtab, uint32_t burst,
+			 uint32_t *seq_dev, struct mi_cls_run *runs_dev, uint32_t run_cap,
+			 struct mi_cls_run_out *out_dev, void *stream);
+int odp_amd_cls_enq_runs_host(odp_pktio_t pktio, const void *res, const uint16_t *len, uint32_t n,
+			      const struct mi_cls_enq_tab *tab, const struct mi_cls_run_tab *rtab,
+			      uint32_t burst, uint32_t *seq, struct mi_cls_run *runs, uint32_t run_cap,
+			      struct mi_cls_run_out *out);
+int odp_amd_cls_enq_runs_host_submit(odp_pktio_t pktio, const void *res, const uint16_t *len,
+				     uint32_t n, const struct mi_cls_enq_tab *tab,
+				     const struct mi_cls_run_tab *rtab, uint32_t burst, uint32_t *seq,
+				     struct mi_cls_run *runs, uint32_t run_cap, struct mi_cls_run_out *out,
+				     uint64_t *ticket);
+int odp_amd_cls_enq_runs_host_wait(odp_pktio_t pktio, uint64_t ticket);
+
 /* Device contexts of the pktio (its GPUs, ODP_AMD_GPUS / create_multi); 1
  * for a single-device pktio, < 0 on error. */
 int odp_amd_cls_devices(odp_pktio_t pktio);

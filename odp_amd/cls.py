@@ -139,6 +139,51 @@ def enq_tab(cos_nq, cos_q0, ent_dst, ndst) -> EnqTab:
     return t
 
 
+# the run plan (include/mi_cls.h): the mode bits, the vector-pool slots, the
+# kernels' shape
+RUN_AGGR, RUN_VEC, RUN_VSLOTS = 1, 2, 16
+RUN_TILE, RUN_GRID = 1024, 256
+RUN_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("dst", "<u2"), ("cos", "u1"), ("flags", "u1"),
+                      ("nvec", "<u4")])
+
+
+class RunTab(C.Structure):
+    """mi_cls_run_tab_t."""
+    _fields_ = [("mode", C.c_uint8 * 256), ("vmax", C.c_uint16 * 256), ("vslot", C.c_uint8 * 256),
+                ("stamp", C.c_uint64)]
+
+
+class RunOut(C.Structure):
+    """mi_cls_run_out_t."""
+    _fields_ = EnqOut._fields_ + [("nruns", C.c_uint64), ("vectors", C.c_uint64),
+                                  ("vec_need", C.c_uint64 * RUN_VSLOTS)]
+
+
+RUN_OUT_WORDS = C.sizeof(RunOut) // 8
+
+
+def run_tab(mode, vmax, vslot) -> RunTab:
+    """A mi_cls_run_tab_t from its arrays (up to 256 values by CoS index), with
+    a stamp no earlier table of this process had."""
+    global _enq_stamps
+    t = RunTab()
+    for name, src in (("mode", mode), ("vmax", vmax), ("vslot", vslot)):
+        a = np.ctypeslib.as_array(getattr(t, name))
+        s = np.asarray(src)
+        a[:s.shape[0]] = s
+    _enq_stamps += 1
+    t.stamp = (1 << 32) + _enq_stamps
+    return t
+
+
+def run_out_dict(words):
+    """The 24 uint64 of a mi_cls_run_out_t as a dict (vec_need: a list)."""
+    w = [int(v) for v in words]
+    d = dict(zip(ENQ_OUT_FIELDS + ("nruns", "vectors"), w))
+    d["vec_need"] = w[8:8 + RUN_VSLOTS]
+    return d
+
+
 # odp_proto_t, odp_proto_layer_t, odp_proto_chksums_t.all_chksum
 PROTO_ETH, PROTO_IPV4, PROTO_IPV6 = 1, 2, 3
 LAYER_L2, LAYER_L3, LAYER_L4, LAYER_ALL = 1, 2, 3, 4
@@ -235,6 +280,22 @@ def _load():
         "odp_amd_cls_enq_plan_host_submit": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), vp, vp, vp,
                                                    C.POINTER(C.c_uint64)]),
         "odp_amd_cls_enq_plan_host_wait": (i32, [vp, C.c_uint64]),
+        "mi_cls_enq_runs": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), C.POINTER(RunTab), u32, vp, vp, u32, vp,
+                                  vp]),
+        "mi_cls_enq_runs_host": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), C.POINTER(RunTab), u32, vp, vp, u32,
+                                       vp]),
+        "mi_cls_enq_runs_host_submit": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), C.POINTER(RunTab), u32, vp, vp,
+                                              u32, vp, C.POINTER(C.c_uint64)]),
+        "mi_cls_enq_runs_host_wait": (i32, [vp, C.c_uint64]),
+        "odp_amd_cls_runtab_fill": (i32, [C.POINTER(RunTab), C.POINTER(vp), C.POINTER(u32),
+                                          C.POINTER(C.c_uint64)]),
+        "odp_amd_cls_enq_runs": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), C.POINTER(RunTab), u32, vp, vp, u32,
+                                       vp, vp]),
+        "odp_amd_cls_enq_runs_host": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), C.POINTER(RunTab), u32, vp, vp,
+                                            u32, vp]),
+        "odp_amd_cls_enq_runs_host_submit": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), C.POINTER(RunTab), u32, vp,
+                                                   vp, u32, vp, C.POINTER(C.c_uint64)]),
+        "odp_amd_cls_enq_runs_host_wait": (i32, [vp, C.c_uint64]),
         "odp_amd_cls_parse_host": (i32, [vp, C.c_size_t, vp, vp, u32, u32, u32, u32, vp]),
         "odp_amd_cls_parse_term": (None, []),
     }
@@ -547,10 +608,82 @@ def _enq_plan_host(L, prefix, handle, res, ln, tab, perm, gbeg, out, submit):
         raise RuntimeError(f"{prefix}: {rc}")
 
 
+def _enq_runs_device(call, handle, records, lens, tab, rtab, burst, run_cap, device, poison=0xA5A5A5A5):
+    """Upload records and lens, run the device form `call` (mi_cls_enq_runs /
+    odp_amd_cls_enq_runs) on torch's current stream and return (seq, runs,
+    out): runs all run_cap entries (RUN_DTYPE; those the call left alone still
+    hold `poison`), out the dict of run_out_dict.  Every output word, and a
+    guard past each array, holds `poison` before the launch."""
+    import torch
+    dev = torch.device(device)
+    rec = np.ascontiguousarray(records, dtype=R.RESULT_DTYPE)
+    n = int(rec.shape[0])
+    ln = np.ascontiguousarray(lens, dtype=np.uint16)
+    assert ln.shape[0] == n
+    t_res = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy() if n else np.zeros(16, np.uint8)).to(dev)
+    t_len = torch.from_numpy(ln.view(np.int16).copy() if n else np.zeros(1, np.int16)).to(dev)
+    t_seq = torch.from_numpy(np.full(n + 1, poison, np.uint32).view(np.int32)).to(dev)
+    t_runs = torch.from_numpy(np.full(4 * (run_cap + 1), poison, np.uint32).view(np.int32)).to(dev)
+    t_out = torch.from_numpy(np.full(2 * (RUN_OUT_WORDS + 1), poison, np.uint32).view(np.int32)).to(dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = call(handle, t_res.data_ptr(), t_len.data_ptr(), n, C.byref(tab), C.byref(rtab), burst,
+              t_seq.data_ptr(), t_runs.data_ptr(), run_cap, t_out.data_ptr(), stream or None)
+    if rc != 0:
+        raise RuntimeError(f"enq_runs: {rc} ({lib().mi_cls_strerror(rc).decode()})")
+    torch.cuda.synchronize(dev)
+    seq = t_seq.cpu().numpy().view(np.uint32)
+    runs = t_runs.cpu().numpy().view(np.uint32)
+    out = t_out.cpu().numpy().view(np.uint32)
+    if seq[n] != poison or np.any(runs[4 * run_cap:] != poison) or out[-1] != poison or out[-2] != poison:
+        raise RuntimeError("enq_runs wrote past an output array")
+    return seq[:n].copy(), runs[:4 * run_cap].copy().view(RUN_DTYPE), run_out_dict(out[:-2].view(np.uint64))
+
+
+def _enq_runs_host(L, prefix, handle, res, ln, tab, rtab, burst, seq, runs, out, submit):
+    """The host forms of `prefix` (mi_cls_enq_runs_host /
+    odp_amd_cls_enq_runs_host) on numpy arrays, as _enq_plan_host.  runs:
+    RUN_DTYPE, its length the run_cap; out: 24 uint64."""
+    n = int(res.shape[0])
+    cap = int(runs.shape[0])
+    args = (handle, res.ctypes.data if n else None, ln.ctypes.data if n else None, n, C.byref(tab),
+            C.byref(rtab), burst, seq.ctypes.data if n else None, runs.ctypes.data if cap else None, cap,
+            out.ctypes.data)
+    if submit:
+        t = C.c_uint64()
+        rc = getattr(L, prefix + "_submit")(*args, C.byref(t))
+        if rc == 0:
+            rc = getattr(L, prefix + "_wait")(handle, t.value)
+    else:
+        rc = getattr(L, prefix)(*args)
+    if rc != 0:
+        raise RuntimeError(f"{prefix}: {rc}")
+
+
 class EnqContext(_FeatureContext):
     """A device context for the enqueue plan (mi_cls_enq_plan and its host
     entries: a classified batch's records grouped by destination queue, the
-    records that are not delivered, the pktio counters); needs no rules."""
+    records that are not delivered, the pktio counters) and the run plan
+    (mi_cls_enq_runs: the same batch cut into the reference's runs, with the
+    packet-vector counts); needs no rules."""
+
+    def runs_device(self, d_res, d_len, n, tab, rtab, burst, d_seq, d_runs, run_cap, d_out, stream=0):
+        """mi_cls_enq_runs on device pointers (ints), stream-ordered.  Returns
+        the C status."""
+        return self.L.mi_cls_enq_runs(self.ctx, d_res or None, d_len or None, n, C.byref(tab), C.byref(rtab),
+                                      burst, d_seq or None, d_runs or None, run_cap, d_out or None,
+                                      stream or None)
+
+    def runs(self, records, lens, tab, rtab, burst=0, run_cap=None, poison=0xA5A5A5A5):
+        """Upload records and lens, plan the runs; returns (seq, runs, out)
+        (run_cap: room for every run by default)."""
+        cap = len(records) if run_cap is None else run_cap
+        return _enq_runs_device(self.L.mi_cls_enq_runs, self.ctx, records, lens, tab, rtab, burst, cap,
+                                f"cuda:{self.gpu}", poison)
+
+    def runs_host(self, res, ln, tab, rtab, burst, seq, runs, out, submit=False):
+        """mi_cls_enq_runs_host (submit: _host_submit / _host_wait)."""
+        _enq_runs_host(self.L, "mi_cls_enq_runs_host", self.ctx, res, ln, tab, rtab, burst, seq, runs, out,
+                       submit)
 
     def plan_device(self, d_res, d_len, n, tab, d_perm, d_gbeg, d_out, stream=0):
         """On device pointers (ints), stream-ordered.  Returns the C status."""
@@ -874,6 +1007,41 @@ class Classifier:
         if tab is None:
             tab = self.enq_table()[0]
         _enq_plan_host(self.L, "odp_amd_cls_enq_plan_host", self.pktio, res, ln, tab, perm, gbeg, out, submit)
+
+    def run_table(self):
+        """The run plan's table of the current control plane
+        (odp_amd_cls_runtab_fill; host only).  Returns (RunTab, vpools, gen):
+        vpools[slot] the vector pool of each slot."""
+        tab = RunTab()
+        p = (C.c_void_p * RUN_VSLOTS)()
+        ns, gen = C.c_uint32(), C.c_uint64()
+        rc = self.L.odp_amd_cls_runtab_fill(C.byref(tab), p, C.byref(ns), C.byref(gen))
+        if rc != 0:
+            raise RuntimeError(f"odp_amd_cls_runtab_fill: {rc}")
+        return tab, [_h(p[i]) for i in range(ns.value)], gen.value
+
+    def enq_runs(self, records, lens, tab=None, rtab=None, burst=0, run_cap=None, device="cuda:0",
+                 poison=0xA5A5A5A5):
+        """The run plan of classified records (odp_amd_cls_enq_runs, on the
+        pktio's context and torch's current stream): returns (seq, runs, out).
+        tab / rtab: enq_table()'s and run_table()'s (default: built now)."""
+        if tab is None:
+            tab = self.enq_table()[0]
+        if rtab is None:
+            rtab = self.run_table()[0]
+        cap = len(records) if run_cap is None else run_cap
+        return _enq_runs_device(self.L.odp_amd_cls_enq_runs, self.pktio, records, lens, tab, rtab, burst, cap,
+                                device, poison)
+
+    def enq_runs_host(self, res, ln, seq, runs, out, tab=None, rtab=None, burst=0, submit=False):
+        """odp_amd_cls_enq_runs_host on numpy arrays (submit: the _submit /
+        _wait pair), as EnqContext.runs_host."""
+        if tab is None:
+            tab = self.enq_table()[0]
+        if rtab is None:
+            rtab = self.run_table()[0]
+        _enq_runs_host(self.L, "odp_amd_cls_enq_runs_host", self.pktio, res, ln, tab, rtab, burst, seq, runs, out,
+                       submit)
 
     def cos_stats_packets(self, cos_handle):
         s = CosStats()

@@ -68,6 +68,17 @@ struct mi_cls_ctx {
 	hipEvent_t enq_ev = nullptr;
 	hipStream_t enq_last = nullptr;
 	bool enq_used = false;
+	// the run plan (mi_cls_enq_runs), likewise: the scratch per record (run_cap
+	// of them) and of fixed size, the staged form's seq and runs (run_st_cap
+	// bytes), the two tables' snapshot and whose copies the device holds
+	uint8_t *d_run = nullptr, *d_run_fix = nullptr, *d_run_st = nullptr;
+	size_t run_cap = 0, run_st_cap = 0;
+	uint8_t *h_run_tab = nullptr;
+	const void *run_tab_src[2] = { nullptr, nullptr };
+	uint64_t run_tab_stamp[2] = { 0, 0 };
+	hipEvent_t run_ev = nullptr;
+	hipStream_t run_last = nullptr;
+	bool run_used = false;
 	// program-specialised flat kernel for the loaded program (null: none)
 	std::shared_ptr<SpecCode> spec;
 	uint32_t batch_hint = 0; // largest batch per call (mi_cls_batch_hint), 0: unknown
@@ -156,6 +167,7 @@ static int preload_kernels(int device)
 			chk(mi_cls_launch_parse(proto, ck != 0, 0, nullptr, ParseArgs{}));
 	chk(mi_cls_launch_lso(0, nullptr, LsoArgs{}));
 	chk(mi_cls_launch_enq(nullptr, EnqArgs{}, 0, true));
+	chk(mi_cls_launch_run(nullptr, RunArgs{}, true));
 	if (bad)
 		return bad;
 	done.insert(device);
@@ -249,6 +261,15 @@ extern "C" int mi_cls_ctx_destroy(mi_cls_ctx_t *c)
 	(void)hipFree(c->d_enq_fix);
 	if (c->h_enq_tab)
 		(void)hipHostFree(c->h_enq_tab);
+	if (c->run_ev) {
+		(void)hipEventSynchronize(c->run_ev);
+		(void)hipEventDestroy(c->run_ev);
+	}
+	(void)hipFree(c->d_run);
+	(void)hipFree(c->d_run_fix);
+	(void)hipFree(c->d_run_st);
+	if (c->h_run_tab)
+		(void)hipHostFree(c->h_run_tab);
 	(void)hipFree(c->d_rx);
 	if (c->h_tab)
 		(void)hipHostFree(c->h_tab);
@@ -1564,6 +1585,254 @@ extern "C" int mi_cls_enq_plan_host_submit(mi_cls_ctx_t *c, const mi_cls_result_
 }
 
 extern "C" int mi_cls_enq_plan_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
+{
+	return feature_host_wait(c, ticket);
+}
+
+// --------------------------------------------------------------- the run plan
+// The run plan's scratch in the context, by the enqueue plan's policy: per
+// record the key (4 B) and a run's head (8 B); of fixed size the two tables'
+// device copies, the blocks' summaries and what the scan makes of them, the
+// totals, the counters and the staged form's out.  The staged form's seq and
+// runs have a buffer of their own (4 B per record + 16 B per run of run_cap).
+#define RUN_FIX_TAB 0u
+#define RUN_FIX_RTAB (RUN_FIX_TAB + ENQ_ALIGN(sizeof(mi_cls_enq_tab_t)))
+#define RUN_FIX_SUM (RUN_FIX_RTAB + ENQ_ALIGN(sizeof(mi_cls_run_tab_t)))
+#define RUN_FIX_PRE (RUN_FIX_SUM + ENQ_ALIGN((size_t)MI_CLS_RUN_GRID * 8u * 4u))
+#define RUN_FIX_TOT (RUN_FIX_PRE + ENQ_ALIGN((size_t)MI_CLS_RUN_GRID * 16u))
+#define RUN_FIX_CTR (RUN_FIX_TOT + ENQ_ALIGN(8u))
+#define RUN_FIX_OUT (RUN_FIX_CTR + ENQ_ALIGN(sizeof(mi_cls_run_out_t)))
+#define RUN_FIX_BYTES (RUN_FIX_OUT + ENQ_ALIGN(sizeof(mi_cls_run_out_t)))
+
+static uint2 *run_head(const mi_cls_ctx_t *c) { return (uint2 *)c->d_run; }
+static uint32_t *run_key(const mi_cls_ctx_t *c) { return (uint32_t *)(c->d_run + ENQ_ALIGN(8u * c->run_cap)); }
+
+// Before the scratch is replaced, and before a table's snapshot or device copy
+// is rewritten, the previous run plan has ended (run_ev).
+static int run_idle(mi_cls_ctx_t *c)
+{
+	if (c->run_used)
+		HIP_OK(hipEventSynchronize(c->run_ev));
+	return 0;
+}
+
+static int run_scratch(mi_cls_ctx_t *c, uint32_t n, size_t staged)
+{
+	if (!c->d_run_fix) {
+		if (!c->run_ev && hipEventCreateWithFlags(&c->run_ev, hipEventDisableTiming) != hipSuccess)
+			return -EIO;
+		if ((!c->h_run_tab &&
+		     hipHostMalloc((void **)&c->h_run_tab, ENQ_ALIGN(sizeof(mi_cls_enq_tab_t)) + sizeof(mi_cls_run_tab_t),
+				   hipHostMallocDefault) != hipSuccess) ||
+		    hipMalloc((void **)&c->d_run_fix, RUN_FIX_BYTES) != hipSuccess)
+			return -ENOMEM;
+	}
+	if (n > c->run_cap) {
+		const int rc = run_idle(c);
+		if (rc)
+			return rc;
+		(void)hipFree(c->d_run);
+		c->d_run = nullptr;
+		c->run_cap = 0;
+		const size_t cap = n < 4096u ? 4096u : (size_t)n + n / 2;
+		if (hipMalloc((void **)&c->d_run, ENQ_ALIGN(8u * cap) + ENQ_ALIGN(4u * cap)) != hipSuccess)
+			return -ENOMEM;
+		c->run_cap = cap;
+	}
+	if (staged > c->run_st_cap) {
+		const int rc = run_idle(c);
+		if (rc)
+			return rc;
+		(void)hipFree(c->d_run_st);
+		c->d_run_st = nullptr;
+		c->run_st_cap = 0;
+		const size_t cap = staged < 65536u ? 65536u : staged + staged / 2;
+		if (hipMalloc((void **)&c->d_run_st, cap) != hipSuccess)
+			return -ENOMEM;
+		c->run_st_cap = cap;
+	}
+	return 0;
+}
+
+// The tables first (host memory, no device needed), then the context, then
+// the batch
+static int run_check(const mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len, uint32_t n,
+		     const mi_cls_enq_tab_t *tab, const mi_cls_run_tab_t *rtab, const uint32_t *seq,
+		     const mi_cls_run_t *runs, uint32_t run_cap, const mi_cls_run_out_t *out)
+{
+	if (!tab || !rtab)
+		return -EINVAL;
+	if (tab->ndst > MI_CLS_ENQ_DST_MAX)
+		return -E2BIG;
+	for (uint32_t i = 0; i < 256u; ++i)
+		if ((rtab->mode[i] & MI_CLS_RUN_VEC) && (rtab->vmax[i] == 0 || rtab->vslot[i] >= MI_CLS_RUN_VSLOTS))
+			return -EINVAL;
+	if (!c)
+		return no_ctx();
+	if (!out || ((uintptr_t)out & 7u) != 0)
+		return -EINVAL;
+	if (n == 0)
+		return 0;
+	return res && len && seq && (run_cap == 0 || (runs && ((uintptr_t)runs & 15u) == 0)) ? 0 : -EINVAL;
+}
+
+// One table's device copy, refreshed when the host table's stamp moved
+static int run_tab_sync(mi_cls_ctx_t *c, int which, const void *tab, uint64_t stamp, size_t bytes, void *snap,
+			void *dtab, hipStream_t st)
+{
+	if (c->run_tab_src[which] && c->run_tab_src[which] == tab && c->run_tab_stamp[which] == stamp)
+		return 0;
+	const int rc = run_idle(c);
+	if (rc)
+		return rc;
+	memcpy(snap, tab, bytes);
+	c->run_tab_src[which] = nullptr;
+	HIP_OK(hipMemcpyAsync(dtab, snap, bytes, hipMemcpyHostToDevice, st));
+	c->run_tab_src[which] = tab;
+	c->run_tab_stamp[which] = stamp;
+	return 0;
+}
+
+extern "C" int mi_cls_enq_runs(mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len, uint32_t n,
+			       const mi_cls_enq_tab_t *tab, const mi_cls_run_tab_t *rtab, uint32_t burst,
+			       uint32_t *seq, mi_cls_run_t *runs, uint32_t run_cap, mi_cls_run_out_t *out,
+			       void *stream)
+{
+	int rc = run_check(c, res, len, n, tab, rtab, seq, runs, run_cap, out);
+	if (rc)
+		return rc;
+	hipStream_t st = (hipStream_t)stream;
+	HIP_OK(set_device(c->device));
+	rc = run_scratch(c, n, 0);
+	if (rc)
+		return rc;
+	// the scratch is one plan's at a time: a plan on another stream follows
+	// the previous one
+	if (c->run_used && c->run_last != st)
+		HIP_OK(hipStreamWaitEvent(st, c->run_ev, 0));
+	mi_cls_enq_tab_t *dtab = (mi_cls_enq_tab_t *)(c->d_run_fix + RUN_FIX_TAB);
+	mi_cls_run_tab_t *drtab = (mi_cls_run_tab_t *)(c->d_run_fix + RUN_FIX_RTAB);
+	const uint32_t ndst = tab->ndst;
+	rc = run_tab_sync(c, 0, tab, tab->stamp, sizeof(*tab), c->h_run_tab, dtab, st);
+	if (!rc)
+		rc = run_tab_sync(c, 1, rtab, rtab->stamp, sizeof(*rtab),
+				  c->h_run_tab + ENQ_ALIGN(sizeof(mi_cls_enq_tab_t)), drtab, st);
+	if (rc)
+		return rc;
+	RunArgs a;
+	memset(&a, 0, sizeof(a));
+	a.res = res;
+	a.len = len;
+	a.tab = dtab;
+	a.rtab = drtab;
+	a.n = n;
+	a.ndst = ndst;
+	const uint64_t tiles = ((uint64_t)n + MI_CLS_RUN_TILE - 1u) / MI_CLS_RUN_TILE;
+	a.grid = (uint32_t)(tiles < MI_CLS_RUN_GRID ? tiles : MI_CLS_RUN_GRID);
+	a.tpb = a.grid ? (uint32_t)((tiles + a.grid - 1u) / a.grid) : 0u;
+	a.burst = burst ? burst : 0xFFFFFFFFu;   // i / burst == 0 for every i < n
+	a.run_cap = run_cap;
+	a.key = run_key(c);
+	a.head = run_head(c);
+	a.sum = (uint32_t *)(c->d_run_fix + RUN_FIX_SUM);
+	a.pre = (uint4 *)(c->d_run_fix + RUN_FIX_PRE);
+	a.tot = (uint32_t *)(c->d_run_fix + RUN_FIX_TOT);
+	a.ctr = (unsigned long long *)(c->d_run_fix + RUN_FIX_CTR);
+	a.seq = seq;
+	a.runs = runs;
+	a.out = out;
+	// this call's counters start from zero, whatever the last one left
+	HIP_OK(hipMemsetAsync(a.ctr, 0, sizeof(mi_cls_run_out_t), st));
+	uint32_t *last = c->last;
+	last[0] = 192u + MI_CLS_RUN_TILE / WAVE;
+	last[1] = n ? 5u : 1u;
+	last[2] = last[3] = last[4] = last[5] = 0;
+	last[6] = a.grid;
+	rc = mi_cls_launch_run(st, a, false);
+	if (rc)
+		return rc;
+	HIP_OK(hipEventRecord(c->run_ev, st));
+	c->run_used = true;
+	c->run_last = st;
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+// A host batch on the context's stream, nothing waited for: in place when
+// every array is page-locked, else the records and lengths through the
+// staging buffers and seq, runs and out through the scratch.  The staged
+// runs go up before they come back: the entries past nruns, which the device
+// alone knows, keep the caller's values.
+static int run_host_launch(mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len, uint32_t n,
+			   const mi_cls_enq_tab_t *tab, const mi_cls_run_tab_t *rtab, uint32_t burst,
+			   uint32_t *seq, mi_cls_run_t *runs, uint32_t run_cap, mi_cls_run_out_t *out)
+{
+	HIP_OK(set_device(c->device));
+	if (n == 0)
+		run_cap = 0;   // no run is written
+	const mi_cls_result_t *zr = res;
+	const uint16_t *zl = len;
+	uint32_t *zs = seq;
+	mi_cls_run_t *zu = runs;
+	mi_cls_run_out_t *zo = out;
+	if (dev_views(zo) && (n == 0 || (dev_views(zr, zl, zs) && (run_cap == 0 || dev_views(zu)))))
+		return mi_cls_enq_runs(c, zr, zl, n, tab, rtab, burst, zs, zu, run_cap, zo, c->stream);
+	const size_t seq_bytes = ENQ_ALIGN((size_t)n * sizeof(uint32_t));
+	const size_t runs_bytes = (size_t)run_cap * sizeof(mi_cls_run_t);
+	int rc = stage_bufs(c, 0, n);
+	if (!rc)
+		rc = run_scratch(c, n, seq_bytes + runs_bytes);
+	if (rc)
+		return rc;
+	uint32_t *dseq = (uint32_t *)c->d_run_st;
+	mi_cls_run_t *druns = (mi_cls_run_t *)(c->d_run_st + seq_bytes);
+	mi_cls_run_out_t *dout = (mi_cls_run_out_t *)(c->d_run_fix + RUN_FIX_OUT);
+	if (n) {
+		HIP_OK(hipMemcpyAsync(c->d_out, res, n * sizeof(mi_cls_result_t), hipMemcpyHostToDevice, c->stream));
+		HIP_OK(hipMemcpyAsync(c->d_len, len, n * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+	}
+	if (runs_bytes)
+		HIP_OK(hipMemcpyAsync(druns, runs, runs_bytes, hipMemcpyHostToDevice, c->stream));
+	rc = mi_cls_enq_runs(c, c->d_out, c->d_len, n, tab, rtab, burst, dseq, druns, run_cap, dout, c->stream);
+	if (rc)
+		return rc;
+	if (n)
+		HIP_OK(hipMemcpyAsync(seq, dseq, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	if (runs_bytes)
+		HIP_OK(hipMemcpyAsync(runs, druns, runs_bytes, hipMemcpyDeviceToHost, c->stream));
+	HIP_OK(hipMemcpyAsync(out, dout, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+	// the scratch is this plan's until the copies have read it
+	HIP_OK(hipEventRecord(c->run_ev, c->stream));
+	return 0;
+}
+
+extern "C" int mi_cls_enq_runs_host(mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len,
+				    uint32_t n, const mi_cls_enq_tab_t *tab, const mi_cls_run_tab_t *rtab,
+				    uint32_t burst, uint32_t *seq, mi_cls_run_t *runs, uint32_t run_cap,
+				    mi_cls_run_out_t *out)
+{
+	const int rc = run_check(c, res, len, n, tab, rtab, seq, runs, run_cap, out);
+	if (rc)
+		return rc;
+	return host_run(c, nullptr,
+			[&] { return run_host_launch(c, res, len, n, tab, rtab, burst, seq, runs, run_cap, out); });
+}
+
+extern "C" int mi_cls_enq_runs_host_submit(mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len,
+					   uint32_t n, const mi_cls_enq_tab_t *tab, const mi_cls_run_tab_t *rtab,
+					   uint32_t burst, uint32_t *seq, mi_cls_run_t *runs, uint32_t run_cap,
+					   mi_cls_run_out_t *out, uint64_t *ticket)
+{
+	if (!ticket)
+		return -EINVAL;
+	*ticket = 0;
+	const int rc = run_check(c, res, len, n, tab, rtab, seq, runs, run_cap, out);
+	if (rc)
+		return rc;
+	return host_run(c, ticket,
+			[&] { return run_host_launch(c, res, len, n, tab, rtab, burst, seq, runs, run_cap, out); });
+}
+
+extern "C" int mi_cls_enq_runs_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
 {
 	return feature_host_wait(c, ticket);
 }

@@ -2924,6 +2924,32 @@ struct EnqArgs {
 // the kernels only.
 int mi_cls_launch_enq(hipStream_t st, const EnqArgs &a, int passes, bool preload);
 
+// the run plan (mi_cls_enq_runs; kernels: mi_cls_run_dev.h, mi_cls_kr.hip)
+struct RunArgs {
+	const mi_cls_result_t *res;
+	const uint16_t *len;
+	const mi_cls_enq_tab_t *tab;   // the device copies
+	const mi_cls_run_tab_t *rtab;
+	uint32_t n;
+	uint32_t ndst;
+	uint32_t grid;                 // blocks of the key and scatter launches
+	uint32_t tpb;                  // tiles per block
+	uint32_t burst;                // records per burst (never 0: 0xFFFFFFFF for one burst)
+	uint32_t run_cap;
+	uint32_t *key;                 // scratch: n keys (id << 8 | cos; RUN_NONE: not delivered)
+	uint2 *head;                   // scratch: per run its first place in seq and its key
+	uint32_t *sum;                 // scratch: RUN_SUM words per block, the key launch's summaries
+	uint4 *pre;                    // scratch: per block what precedes it (the scan's result)
+	uint32_t *tot;                 // scratch: the delivered records, the runs
+	unsigned long long *ctr;       // scratch: mi_cls_run_out_t, zeroed before the launches
+	uint32_t *seq;
+	mi_cls_run_t *runs;
+	mi_cls_run_out_t *out;
+};
+// The run plan's launches on `st`, in order: key, scan, scatter, finish, out;
+// n == 0: out alone.  preload: resolve the kernels only.
+int mi_cls_launch_run(hipStream_t st, const RunArgs &a, bool preload);
+
 // Every launcher goes through mi_launch.  grid == 0 launches nothing: it
 // resolves the instantiation on the current device (hipFuncGetAttributes
 // loads the code object that holds it), so mi_cls_ctx_create can load every

@@ -1503,6 +1503,104 @@ int odp_amd_cls_enq_plan_host_wait(odp_pktio_t h, uint64_t ticket)
 	return ticket && e->ctx ? mi_cls_enq_plan_host_wait(e->ctx, ticket) : ticket ? -EINVAL : 0;
 }
 
+/* The run plan's table (mi_cls_run_tab_t, mi_cls.h) of the current control
+ * plane, from what odp_amd_cls_cos_enq_mode reads: per CoS index whether its
+ * runs go to the queue's aggregator, whether they leave as packet vectors, a
+ * vector's size and the slot of its pool, slots numbered in order of first
+ * appearance scanning CoS index (CoS with the same pool share one).  A CoS
+ * whose action is DROP has no mode.  vpools[] (room for MI_CLS_RUN_VSLOTS):
+ * each slot's pool; *nslots: slots in use; *gen: the generation the table
+ * reflects.  Needs no device.  -E2BIG past MI_CLS_RUN_VSLOTS pools. */
+int odp_amd_cls_runtab_fill(struct mi_cls_run_tab *tab, odp_pool_t vpools[], uint32_t *nslots,
+			    uint64_t *gen)
+{
+	static uint64_t stamps;   /* under G.lock */
+	uint32_t ns = 0;
+	int rc = 0;
+
+	if (!tab || !vpools || !nslots || !gen)
+		return -EINVAL;
+	memset(tab, 0, sizeof(*tab));
+	pthread_mutex_lock(&G.lock);
+	*gen = G.gen;
+	for (uint32_t i = 0; G.init && i < G.max_cos && i < 256; i++) {
+		const cos_t *c = &G.cos[i];
+
+		if (!c->valid || c->action != ODP_COS_ACTION_ENQUEUE)
+			continue;
+		if (c->use_aggr)
+			tab->mode[i] |= MI_CLS_RUN_AGGR;
+		if (c->use_std_enq)
+			continue;
+		uint32_t k = 0;
+
+		while (k < ns && vpools[k] != c->vec_pool)
+			k++;
+		if (c->vec_max > 0xFFFFu || (k == ns && ns == MI_CLS_RUN_VSLOTS)) {
+			rc = -E2BIG;
+			break;
+		}
+		if (k == ns)
+			vpools[ns++] = c->vec_pool;
+		tab->mode[i] |= MI_CLS_RUN_VEC;
+		tab->vmax[i] = (uint16_t)c->vec_max;
+		tab->vslot[i] = (uint8_t)k;
+	}
+	tab->stamp = ++stamps;
+	pthread_mutex_unlock(&G.lock);
+	*nslots = ns;
+	return rc;
+}
+
+int odp_amd_cls_enq_runs(odp_pktio_t h, const void *res_dev, const uint16_t *len_dev, uint32_t n,
+			 const struct mi_cls_enq_tab *tab, const struct mi_cls_run_tab *rtab, uint32_t burst,
+			 uint32_t *seq_dev, struct mi_cls_run *runs_dev, uint32_t run_cap,
+			 struct mi_cls_run_out *out_dev, void *stream)
+{
+	mi_cls_ctx_t *c;
+	const int rc = enq_ctx(h, &c);
+
+	return rc ? rc : mi_cls_enq_runs(c, (const mi_cls_result_t *)res_dev, len_dev, n, tab, rtab, burst,
+					 seq_dev, runs_dev, run_cap, out_dev, stream);
+}
+
+int odp_amd_cls_enq_runs_host(odp_pktio_t h, const void *res, const uint16_t *len, uint32_t n,
+			      const struct mi_cls_enq_tab *tab, const struct mi_cls_run_tab *rtab,
+			      uint32_t burst, uint32_t *seq, struct mi_cls_run *runs, uint32_t run_cap,
+			      struct mi_cls_run_out *out)
+{
+	mi_cls_ctx_t *c;
+	const int rc = enq_ctx(h, &c);
+
+	return rc ? rc : mi_cls_enq_runs_host(c, (const mi_cls_result_t *)res, len, n, tab, rtab, burst, seq,
+					      runs, run_cap, out);
+}
+
+int odp_amd_cls_enq_runs_host_submit(odp_pktio_t h, const void *res, const uint16_t *len, uint32_t n,
+				     const struct mi_cls_enq_tab *tab, const struct mi_cls_run_tab *rtab,
+				     uint32_t burst, uint32_t *seq, struct mi_cls_run *runs, uint32_t run_cap,
+				     struct mi_cls_run_out *out, uint64_t *ticket)
+{
+	mi_cls_ctx_t *c;
+	int rc;
+
+	if (!ticket)
+		return -EINVAL;
+	*ticket = 0;
+	rc = enq_ctx(h, &c);
+	return rc ? rc : mi_cls_enq_runs_host_submit(c, (const mi_cls_result_t *)res, len, n, tab, rtab, burst,
+						     seq, runs, run_cap, out, ticket);
+}
+
+int odp_amd_cls_enq_runs_host_wait(odp_pktio_t h, uint64_t ticket)
+{
+	pktio_t *e = get_pktio(h);
+
+	if (!e)
+		return -EINVAL;
+	return ticket && e->ctx ? mi_cls_enq_runs_host_wait(e->ctx, ticket) : ticket ? -EINVAL : 0;
+}
+
 /* One burst's receive chain (mi_cls_rx_chain_submit) on the pktio's
  * context, under the current rules.  -ENOTSUP for pktios over several
  * devices (they take the host-decided delivery). */
