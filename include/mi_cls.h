@@ -335,8 +335,9 @@ int mi_cls_batch_hint(mi_cls_ctx_t *ctx, uint32_t max_batch);
  *   A checksum is inserted when the packet is of its protocol and
  *   (<l>_chksum_set ? <l>_chksum : the pktout_opt bit): IPv4 under the L3
  *   pair, UDP (17) / TCP (6) / SCTP (132) under the L4 pair.  pktout_opt is
- *   odp_pktout_config_opt_t.all_bits: bits 4-7 ipv4 / udp / tcp / sctp
- *   _chksum (the _ena bits 0-3 are not consulted, as in loop.c).
+ *   odp_pktout_config_opt_t.all_bits >> 1 (all_bits without ts_ena, its bit
+ *   0): bits 4-7 ipv4 / udp / tcp / sctp _chksum (the _ena bits 0-3 are not
+ *   consulted, as in loop.c).
  *   IPv4: over the 4 IHL header bytes, stored at l3 + 10; not when IHL < 5
  *   or the header ends past the frame.  UDP / TCP: pseudo header from the
  *   addresses as stored, the protocol, and the UDP length field as stored

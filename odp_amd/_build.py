@@ -20,7 +20,8 @@
   oracle/_ref/libodp_ref.so, oracle/_ref/ref_shim_main
                          test infrastructure: the reference's parser, checksum
                          and classifier sources, compiled UNCHANGED, with
-                         oracle/ref_shim.c, as a library (oracle/reflib.py) and
+                         oracle/ref_shim.c and ref_loop_shim.c (the loop
+                         pktio's transmit code), as a library (oracle/reflib.py) and
                          as a sanitised stand-alone program; same rule
 """
 from __future__ import annotations

@@ -22,7 +22,7 @@
 #pragma once
 #include "mi_cls_dev.h"
 
-#define TX_OPT_IPV4 (1u << 4)   // odp_pktout_config_opt_t.all_bits: <proto>_chksum
+#define TX_OPT_IPV4 (1u << 4)   // odp_pktout_config_opt_t.all_bits >> 1: <proto>_chksum
 #define TX_OPT_UDP (1u << 5)
 #define TX_OPT_TCP (1u << 6)
 #define TX_OPT_SCTP (1u << 7)

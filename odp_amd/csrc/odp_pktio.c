@@ -356,7 +356,7 @@ int odp_pktio_config(odp_pktio_t h, const odp_pktio_config_t *config)
 		config = &def;
 	}
 	/* parser options, pktin checksum validation and drop-on-error options
-	 * (bits 2-10), pktout checksum insertion on a loop pktio (bits 0-7); no
+	 * (bits 2-10), pktout checksum insertion on a loop pktio (bits 1-8); no
 	 * timestamps, other pktout offloads or IPsec; enable_lso is accepted
 	 * (LSO is common code over every driver, odp_packet_io.c:3305) */
 	if ((config->pktin.all_bits & ~RT_PKTIN_OPT_MASK) ||

@@ -157,9 +157,9 @@ void tx_free(rt_pktio_t *e)
  * is taken here. */
 static int tx_chksum(rt_pktio_t *e, const odp_packet_t pkts[], int num, uint8_t *dst, uint32_t index)
 {
-	const uint64_t opt = e->config.pktout.all_bits & RT_PKTOUT_OPT_MASK;
+	const uint64_t opt = RT_PKTOUT_TX_WORD(e->config.pktout.all_bits);
 	const uint32_t hp = dst ? e->hash_proto : 0;
-	int want = (opt & 0xF0u) != 0;
+	int want = (opt & RT_PKTOUT_TX_CK) != 0;
 
 	for (int i = 0; !want && i < num; i++) {
 		const uint32_t f = rt_pkt_hdr(pkts[i])->tx_ck;

@@ -22,8 +22,12 @@
  * sctp checksum validation and the five drop-on-error options */
 #define RT_PKTIN_OPT_MASK 0x7FCull
 /* odp_pktout_config_opt_t bits a loop pktio implements: the four checksum
- * insertion defaults (bits 4-7) and their per-packet override enables (0-3) */
-#define RT_PKTOUT_OPT_MASK 0xFFull
+ * insertion defaults (bits 5-8) and their per-packet override enables (1-4);
+ * bit 0 is ts_ena, which it does not.  The option word of
+ * mi_cls_chksum_insert (include/mi_cls.h) is these bits without bit 0. */
+#define RT_PKTOUT_OPT_MASK 0x1FEull
+#define RT_PKTOUT_TX_WORD(all_bits) (((all_bits) & RT_PKTOUT_OPT_MASK) >> 1)
+#define RT_PKTOUT_TX_CK 0xF0ull   /* ipv4 / udp / tcp / sctp _chksum of that word */
 #define RT_PKT_HEADROOM 128
 #define RT_PKT_TAILROOM 64
 

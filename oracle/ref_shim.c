@@ -19,6 +19,8 @@
  *      odp_cls_* / odp_cos_* / odp_pktio_*_cos_set function), a batch
  *      classify that runs the receive order of pktio/loop.c over a fake
  *      odp_packet_hdr_t, and odp_packet_parse on the same fake packet.
+ * The transmit side (ref_tx_*) is in ref_loop_shim.c; ref_shim.h is what the
+ * two share.
  *
  * Everything is single-threaded.  The reference never returns from a CoS
  * cycle (match_pmr_cos), so ref_classify_batch refuses a table whose rule
@@ -38,6 +40,8 @@
 #include <odp/api/plat/event_inline_types.h>
 #include <odp/api/plat/pool_inline_types.h>
 
+#include "ref_shim.h"
+
 #include <stdarg.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -54,9 +58,8 @@ _Static_assert(ODP_PMR_LEN == 0 && ODP_PMR_CUSTOM_L3 == 20 && ODP_PMR_INNER_HDR_
 _Static_assert(ODP_COS_ACTION_ENQUEUE == 0 && ODP_COS_ACTION_DROP == 1, "action numbers");
 
 /* ============================================================ stand-ins */
-/* A call that the parse / match / table code can never make ends the run:
- * returning something made up would hide a wrong shim. */
-#define UNREACHED() do { fprintf(stderr, "ref_shim: %s called\n", __func__); abort(); } while (0)
+/* A call that the parse / match / table code can never make ends the run
+ * (UNREACHED, ref_shim.h). */
 
 /* --- shared memory: one zeroed heap block per reserve */
 odp_shm_t odp_shm_reserve(const char *name, uint64_t size, uint64_t align, uint32_t flags)
@@ -258,8 +261,6 @@ _Static_assert(sizeof(ref_result_t) == 16, "result record is 16 bytes");
 
 enum { OUT_ENQ = 0, OUT_COS_DROP = 1, OUT_DISCARD = 2, OUT_PARSE_DROP = 3 };
 
-#define TAIL_ZEROS 256   /* "bytes at or beyond frame_len read as zero" */
-
 static odp_pktin_config_opt_t pktin_opt;
 
 /* Tables zeroed, no default / error CoS, options off.  The table sizes are
@@ -406,7 +407,7 @@ static int has_cycle(void)
 
 /* A packet header over a private copy of the frame followed by TAIL_ZEROS
  * zero bytes: one segment, no pool behind it. */
-static odp_packet_hdr_t *fake_packet(const uint8_t *frame, uint32_t len, uint8_t **data)
+odp_packet_hdr_t *ref_fake_packet(const uint8_t *frame, uint32_t len, uint8_t **data)
 {
 	static odp_packet_hdr_t hdr;
 
@@ -457,7 +458,7 @@ static uint16_t queue_slot(uint32_t cos_index, odp_queue_t q)
 static int classify_one(const uint8_t *frame, uint32_t len, ref_result_t *o)
 {
 	uint8_t *data;
-	odp_packet_hdr_t *hdr = fake_packet(frame, len, &data);
+	odp_packet_hdr_t *hdr = ref_fake_packet(frame, len, &data);
 	odp_pool_t pool = ODP_POOL_INVALID;
 	int r;
 
@@ -522,7 +523,7 @@ int ref_packet_parse(const uint8_t *frame, uint32_t len, uint32_t offset, int pr
 		     uint32_t chksums, ref_parse_out_t *out)
 {
 	uint8_t *data;
-	odp_packet_hdr_t *hdr = fake_packet(frame, len, &data);
+	odp_packet_hdr_t *hdr = ref_fake_packet(frame, len, &data);
 	odp_packet_parse_param_t param;
 	odp_packet_parse_result_t res;
 
@@ -557,7 +558,8 @@ int ref_packet_parse(const uint8_t *frame, uint32_t len, uint32_t offset, int pr
 
 #ifdef REF_SHIM_MAIN
 /*
- * ref_shim_main CORPUS OUT: a stand-alone program over the same code, for a
+ * ref_shim_main CORPUS OUT: a stand-alone program over the same code (a
+ * transmit corpus, "RST1": see tx_main below), for a
  * run under the host sanitizers (the fake packet headers and the zero tail
  * are what could be read out of bounds).  CORPUS, written by
  * oracle/reflib.py write_corpus(), all little-endian:
@@ -586,6 +588,65 @@ static void rd(FILE *f, void *p, size_t n)
 	need(fread(p, 1, n, f) == n, "corpus truncated");
 }
 
+/*
+ * A transmit corpus (oracle/reflib.py write_tx_corpus()), all little-endian:
+ *   "RST1", u32 n_opts and the pktout option words, u32 n_hps and the
+ *   hash_proto words, u32 n_cases, then per case u16 len, u16 l3, u16 l4,
+ *   u8 flags and the bytes.
+ * OUT receives, per option word and case, the frame as ref_tx_fix_checksums
+ * leaves it, then per hash_proto word and case the six queue indices of
+ * ref_tx_dest_queue_batch.  Every frame lives in a heap block of its exact
+ * size, and so does every output.
+ */
+static int tx_main(FILE *f, FILE *o)
+{
+	uint32_t n_opts, n_hps, n, i, k, opts[64], hps[64];
+	long at;
+
+	rd(f, &n_opts, 4);
+	need(n_opts <= 64, "too many option rows");
+	rd(f, opts, 4 * n_opts);
+	rd(f, &n_hps, 4);
+	need(n_hps <= 64, "too many hash_proto rows");
+	rd(f, hps, 4 * n_hps);
+	rd(f, &n, 4);
+	at = ftell(f);
+	for (k = 0; k < n_opts + n_hps; k++) {
+		need(fseek(f, at, SEEK_SET) == 0, "seek");
+		for (i = 0; i < n; i++) {
+			ref_tx_desc_t d = { 0 };
+			uint32_t zero = 0;
+			uint16_t len;
+			uint8_t *fr, *out;
+
+			rd(f, &len, 2);
+			rd(f, &d.l3, 2);
+			rd(f, &d.l4, 2);
+			rd(f, &d.flags, 1);
+			fr = malloc(len ? len : 1);
+			need(fr != NULL, "memory");
+			rd(f, fr, len);
+			if (k < n_opts) {
+				out = malloc(len ? len : 1);
+				need(out != NULL, "memory");
+				need(ref_tx_fix_checksums(fr, len, d.l3, d.l4, d.flags, opts[k], out) == 0, "fix");
+				need(fwrite(out, 1, len, o) == len, "write");
+			} else {
+				out = malloc(REF_TX_NMOD);
+				need(out != NULL, "memory");
+				need(ref_tx_dest_queue_batch(fr, &zero, &len, &d, 1, hps[k - n_opts], 5, out) == 0,
+				     "dest queue");
+				need(fwrite(out, 1, REF_TX_NMOD, o) == REF_TX_NMOD, "write");
+			}
+			free(out);
+			free(fr);
+		}
+	}
+	need(fclose(o) == 0, "close");
+	fclose(f);
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
 	static const uint32_t offs[3] = { 0, 2, 19 };
@@ -600,6 +661,8 @@ int main(int argc, char **argv)
 	o = fopen(argv[2], "wb");
 	need(f && o, "cannot open files");
 	rd(f, magic, 4);
+	if (!memcmp(magic, "RST1", 4))
+		return tx_main(f, o);
 	need(!memcmp(magic, "RSC1", 4), "bad magic");
 	rd(f, &opt, 8);
 	need(ref_reset() == 0, "reset");

@@ -1,5 +1,7 @@
 """ctypes binding of oracle/_ref/libodp_ref.so: the reference's OWN parser,
-checksum and classifier sources, compiled unchanged, behind ref_shim.c.
+checksum and classifier sources, compiled unchanged, behind ref_shim.c, and
+the loop pktio's transmit code (checksum insertion, pktin flow hash) behind
+ref_loop_shim.c.
 
 *** TEST INFRASTRUCTURE ***  Only tests/ may import this module.  The library
 is built by odp_amd._build.build() (oracle/Makefile ref-lib) where the
@@ -144,6 +146,95 @@ def packet_parse(frame: bytes, offset: int, proto: int, layer: int, chksums: int
     assert lib().ref_packet_parse(b.ctypes.data, len(frame), offset, proto, layer, chksums,
                                   C.byref(out)) == 0
     return out
+
+
+# ------------------------------------------------------------ transmit side
+# ref_loop_shim.c: the reference's loopback_fix_checksums and get_dest_queue
+# (pktio/loop.c) on the same fake packet.
+
+# The reference exposes only hash % num_qs.  These six moduli are pairwise
+# coprime, none exceeds the loop pktio's 64 queues, and their product
+# 42 300 054 720 exceeds 2^32: by the Chinese remainder theorem, agreement on
+# all six residues is agreement on all 32 bits of the hash.
+TX_MODULI = (64, 63, 61, 59, 55, 53)
+
+# The transmit entries are bound from a second link of the same objects:
+# _ref/libodp_ref.so is also what an oracle/ from before ref_loop_shim.c
+# builds, without them, when such an older checker runs beside this build.
+TX_LIB = os.path.join(HERE, "_ref", "libodp_ref_tx.so")
+_tx_lib = None
+
+
+def tx_lib():
+    global _tx_lib
+    if _tx_lib is None:
+        assert os.path.exists(TX_LIB), (f"{TX_LIB} is missing: odp_amd._build.build() makes it where the "
+                                        "reference tree is present (oracle/Makefile ref-lib)")
+        L = C.CDLL(TX_LIB)
+        vp, i32, u32 = C.c_void_p, C.c_int, C.c_uint32
+        L.ref_tx_fix_checksums.argtypes = [vp, u32, u32, u32, u32, u32, vp]
+        L.ref_tx_dest_queue.argtypes = [vp, u32, u32, u32, u32, u32, u32, i32]
+        L.ref_tx_fix_checksums_batch.argtypes = [vp, vp, vp, vp, u32, u32, vp]
+        L.ref_tx_dest_queue_batch.argtypes = [vp, vp, vp, vp, u32, u32, i32, vp]
+        _tx_lib = L
+    return _tx_lib
+
+
+def tx_fix_checksums_one(frame: bytes, l3: int, l4: int, flags: int, opt: int) -> bytes:
+    """loopback_fix_checksums on one frame: l3 / l4 (0xFFFF: invalid), the
+    descriptor's four override bits, pktout_cfg.all_bits = opt (ipv4_chksum
+    is bit 5 there: tests.tx_model.all_bits of a kernel option word)."""
+    src = np.frombuffer(frame, dtype=np.uint8) if frame else np.zeros(1, np.uint8)
+    out = np.zeros(max(1, len(frame)), np.uint8)
+    assert tx_lib().ref_tx_fix_checksums(src.ctypes.data, len(frame), l3, l4, flags, opt, out.ctypes.data) == 0
+    return bytes(out[:len(frame)])
+
+
+def tx_dest_queue_one(frame: bytes, l3: int, l4: int, meta_flags: int, hash_proto: int, num_qs: int,
+                      index: int = 0) -> int:
+    """get_dest_queue on one frame: the index of the loop queue it picks."""
+    src = np.frombuffer(frame, dtype=np.uint8) if frame else np.zeros(1, np.uint8)
+    q = tx_lib().ref_tx_dest_queue(src.ctypes.data, len(frame), l3, l4, meta_flags, hash_proto, num_qs, index)
+    assert q >= 0, q
+    return q
+
+
+def _tx_args(buf, off, length, desc):
+    assert desc.dtype.itemsize == 8 and len(desc) == len(off) == len(length)
+    return (np.ascontiguousarray(buf), np.ascontiguousarray(off, dtype=np.uint32),
+            np.ascontiguousarray(length, dtype=np.uint16), np.ascontiguousarray(desc))
+
+
+def tx_fix_checksums(buf, off, length, desc, opt):
+    """What tests.tx_model.apply takes, with opt as pktout_cfg.all_bits: the
+    new buffer (no done bytes: the reference has none)."""
+    buf, off, length, desc = _tx_args(buf, off, length, desc)
+    out = buf.copy()
+    assert tx_lib().ref_tx_fix_checksums_batch(buf.ctypes.data, off.ctypes.data, length.ctypes.data,
+                                            desc.ctypes.data, len(off), opt, out.ctypes.data) == 0
+    return out
+
+
+def tx_dest_queues(buf, off, length, desc, hash_proto, index=0):
+    """What tests.txq_model.apply takes: an (n, 6) array, get_dest_queue's
+    queue index for num_qs = each of TX_MODULI."""
+    buf, off, length, desc = _tx_args(buf, off, length, desc)
+    res = np.zeros((len(off), len(TX_MODULI)), np.uint8)
+    assert tx_lib().ref_tx_dest_queue_batch(buf.ctypes.data, off.ctypes.data, length.ctypes.data,
+                                         desc.ctypes.data, len(off), hash_proto, index,
+                                         res.ctypes.data) == 0
+    return res
+
+
+def write_tx_corpus(path, cases, opts, hash_protos):
+    """[(frame, l3, l4, flags)] and the option / hash_proto rows in the
+    format ref_shim.c's main reads ("RST1")."""
+    with open(path, "wb") as f:
+        f.write(b"RST1" + struct.pack("<I", len(opts)) + struct.pack(f"<{len(opts)}I", *opts))
+        f.write(struct.pack("<I", len(hash_protos)) + struct.pack(f"<{len(hash_protos)}I", *hash_protos))
+        f.write(struct.pack("<I", len(cases)))
+        for fr, l3, l4, flags in cases:
+            f.write(struct.pack("<HHHB", len(fr), l3, l4, flags) + fr)
 
 
 # ------------------------------------------------- corpus of ref_shim_main

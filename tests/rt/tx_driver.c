@@ -92,7 +92,7 @@ static int surface(const char *pcap, odp_pool_t pool)
 			return 4;
 		printf("CAP %s 0x%" PRIx64 "\n", tag, (uint64_t)capa.config.pktout.all_bits);
 		/* the eight checksum bits, each default alone, and a bit past them */
-		const uint64_t tries[] = { 0xFF, 0x10, 0x20, 0x40, 0x80, 0x0F, 0x100 };
+		const uint64_t tries[] = { 0x1FE, 0x20, 0x40, 0x80, 0x100, 0x1E, 0x200, 0x01, 0x1FF };
 
 		for (unsigned t = 0; t < sizeof(tries) / sizeof(tries[0]); t++) {
 			odp_pktio_config_init(&cfg);

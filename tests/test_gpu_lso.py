@@ -467,7 +467,7 @@ def test_runtime_segments_pass_checksum_validation(built, gpu, tmp_path, env):
     the checksum insertion of the send, verify on receive.  The pageable pool
     takes both through their bounce buffers, with the same bytes."""
     items = [it for it in golden_items() if it[3] == P_IPV4]
-    lines = flow_head(pktout=0x10, pktin=0x4) + [f"pkt {fr.hex()} {l3_arg(l3)} {p} {hdr} {mp}"
+    lines = flow_head(pktout=0x20, pktin=0x4) + [f"pkt {fr.hex()} {l3_arg(l3)} {p} {hdr} {mp}"
                                                 for fr, hdr, mp, p, l3 in items]
     ev = run_flow(tmp_path, lines + ["send none", "recv", "free", "stats"], env=env)
     assert [f for t, f in ev if t == "R"] == [[str(len(items))]]

@@ -363,7 +363,7 @@ def _round_trip(tmp_path, pktout, pktin, ovr, env=None):
     write_pcap(pcap, [f for f, _, _ in items])
     e = dict(os.environ)
     e.update(env or {})
-    r = subprocess.run([TX_DRIVER, "loop", pcap, hex(pktout), hex(pktin), str(ovr)],
+    r = subprocess.run([TX_DRIVER, "loop", pcap, hex(TX.all_bits(pktout)), hex(pktin), str(ovr)],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, env=e)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     pk, stats, sends = [], None, None

@@ -349,7 +349,8 @@ def mq_run(tmp_path, frames, mode, nq, hp, nout=1, pktout=0, qsize=0, env=None):
     write_pcap(pcap, frames)
     e = dict(os.environ)
     e.update(env or {})
-    r = subprocess.run([MQ_DRIVER, "loop", pcap, mode, str(nq), hex(hp), str(nout), hex(pktout), str(qsize)],
+    r = subprocess.run([MQ_DRIVER, "loop", pcap, mode, str(nq), hex(hp), str(nout), hex(TX.all_bits(pktout)),
+                        str(qsize)],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, env=e)
     assert r.returncode == 0, (r.returncode, r.stdout[-1500:], r.stderr[-2000:])
     out = {"P": [], "SENT": [], "QS": {}, "OS": {}, "U": None}
@@ -472,7 +473,8 @@ def test_single_queue_send_unchanged(built, gpu, tmp_path):
     exp = [TX.insert(f, l3, l4, 0, TX.ALL_TX)[0] for f, l3, l4, _ in items]
     check_arrivals(out, exp, [0] * len(frames), 1)
     pcap = str(tmp_path / "mq.pcap")
-    r = subprocess.run([os.path.join(ROOT, "tests", "_bin", "tx_driver"), "loop", pcap, hex(TX.ALL_TX), "0", "0"],
+    r = subprocess.run([os.path.join(ROOT, "tests", "_bin", "tx_driver"), "loop", pcap, hex(TX.all_bits(TX.ALL_TX)),
+                        "0", "0"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120,
                        env=dict(os.environ, TX_COUNT_ONLY="1"))
     assert r.returncode == 0, r.stderr[-2000:]

@@ -97,16 +97,21 @@ def surface(built, tmp_path_factory):
 
 def test_loop_capability_reports_pktout_checksums(surface):
     caps = {p[1]: int(p[2], 16) for p in surface if p[0] == "CAP"}
-    assert caps["loop"] == TX.ALL_TX | TX.ALL_ENA
+    assert caps["loop"] == TX.all_bits(TX.ALL_TX | TX.ALL_ENA) == 0x1FE
     assert caps["pcap"] == 0
 
 
 def test_loop_config_accepts_pktout_checksums(surface):
     cfg = {(p[1], int(p[2], 16)): int(p[3]) for p in surface if p[0] == "CFG"}
-    for bits in (0xFF, TX.CK_IPV4, TX.CK_UDP, TX.CK_TCP, TX.CK_SCTP, TX.ALL_ENA):
+    for opt in (TX.ALL_TX | TX.ALL_ENA, TX.CK_IPV4, TX.CK_UDP, TX.CK_TCP, TX.CK_SCTP, TX.ALL_ENA):
+        bits = TX.all_bits(opt)
         assert cfg[("loop", bits)] == 0, hex(bits)
         assert cfg[("pcap", bits)] == -1, hex(bits)
-    assert cfg[("loop", 0x100)] == -1 and cfg[("pcap", 0x100)] == -1
+    # the bits are the reference header's: ipv4_chksum is bit 5 (bit 0 is ts_ena)
+    assert [TX.all_bits(o) for o in (TX.CK_IPV4, TX.CK_SCTP, TX.ALL_ENA)] == [0x20, 0x100, 0x1E]
+    # no_packet_refs (bit 9) and ts_ena (bit 0) are not offered
+    for bits in (0x200, TX.TS_ENA, TX.TS_ENA | TX.all_bits(TX.ALL_TX | TX.ALL_ENA)):
+        assert cfg[("loop", bits)] == -1 and cfg[("pcap", bits)] == -1, hex(bits)
 
 
 def test_override_setters_exist(surface):

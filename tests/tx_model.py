@@ -13,11 +13,20 @@ import numpy as np
 
 from tests import chksum_frames as CK
 
-# odp_pktout_config_opt_t.all_bits (include/odp_rt.h)
+# The option word of mi_cls_chksum_insert: odp_pktout_config_opt_t.all_bits
+# (include/odp_rt.h) without its bit 0, ts_ena
 ENA_IPV4, ENA_UDP, ENA_TCP, ENA_SCTP = 1 << 0, 1 << 1, 1 << 2, 1 << 3
 CK_IPV4, CK_UDP, CK_TCP, CK_SCTP = 1 << 4, 1 << 5, 1 << 6, 1 << 7
 ALL_TX = CK_IPV4 | CK_UDP | CK_TCP | CK_SCTP
 ALL_ENA = ENA_IPV4 | ENA_UDP | ENA_TCP | ENA_SCTP
+TS_ENA = 1      # all_bits bit 0: not a checksum option, not offered
+
+
+def all_bits(opt: int) -> int:
+    """odp_pktout_config_opt_t.all_bits of an option word: what a pktio is
+    configured with and what the reference's loopback_fix_checksums reads
+    (ipv4_chksum is bit 5 there)."""
+    return opt << 1
 
 # mi_cls_tx_desc_t.flags
 L3_SET, L3_CK, L4_SET, L4_CK = 1, 2, 4, 8
