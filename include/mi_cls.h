@@ -185,7 +185,11 @@ int mi_cls_rules_load(mi_cls_ctx_t *ctx, const void *tbl, size_t bytes, void *st
  *             allocation ends right after its last frame needs 16 B of slack).
  *   off_dev   uint32 byte offsets, len_dev uint16 frame lengths (FCS stripped)
  *   out_dev   n result records
+ *   n         at most MI_CLS_MAX_BATCH: the kernels address the records
+ *             through a buffer descriptor, whose byte range is 32 bits wide
+ *             (-EINVAL above it)
  * Stream-ordered on `stream`; returns after the launch is enqueued. */
+#define MI_CLS_MAX_BATCH ((1u << 28) - 1u)
 int mi_cls_classify(mi_cls_ctx_t *ctx, const uint8_t *pkts_dev, const uint32_t *off_dev,
 		    const uint16_t *len_dev, uint32_t n, mi_cls_result_t *out_dev,
 		    void *stream);

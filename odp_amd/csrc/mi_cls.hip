@@ -579,7 +579,7 @@ extern "C" int mi_cls_classify(mi_cls_ctx_t *c, const uint8_t *pkts, const uint3
 		return 0;
 	if (!pkts || !off || !len || !out)
 		return -EINVAL;
-	if (((uintptr_t)out & 15u) != 0)
+	if (((uintptr_t)out & 15u) != 0 || n > MI_CLS_MAX_BATCH)
 		return -EINVAL;
 	HIP_OK(hipSetDevice(c->device));
 	KArgs a;

@@ -2117,10 +2117,37 @@ template <typename T> __device__ __forceinline__ uint32_t ld_desc(const T *p)
 // the records are not read again by this kernel, and streaming them out
 // instead of leaving 16 MB of dirty lines in L2 for the end-of-kernel
 // release cut 4-6 % per launch on every config (cached stores measured).
+// The parse kernel's store (mi_cls_parse_dev.h); the classification kernels
+// use the write-through form below.
 __device__ __forceinline__ void store_rec(mi_cls_result_t *dst, uint4 r)
 {
 	u32x4 v = { r.x, r.y, r.z, r.w };
 	__builtin_nontemporal_store(v, (u32x4 *)dst);
+}
+
+// The classification kernels' record store: the same coalesced dwordx4 store
+// per lane (1 KB per wave), written through L2 (buffer store, auxiliary bit
+// 16 = sc1).  Measured: config 3 0.38-0.46 us per launch less than with the
+// nontemporal store (profiles/r08_edges_ab.txt; sc0 sc1 the same within
+// noise).  Supposed, not shown: a nontemporal store leaves its line dirty in
+// the XCD's L2 and a write-through line has left it, so less is written back
+// while the launch runs and when it ends -- but write-through for a wave's
+// last two tiles only gained nothing, so the end-of-launch release alone is
+// not the explanation (Kernel).  Only as 16-B stores: narrower
+// write-through stores are one fabric write each and several times slower
+// per byte.
+// out_rs covers exactly the launch's n records (rec_rsrc), so a store past
+// them is dropped by the hardware's range check.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rec_rsrc(mi_cls_result_t *out, uint32_t n)
+{
+	// n <= MI_CLS_MAX_BATCH (mi_cls_classify): 16 n fits the 32-bit range
+	return __builtin_amdgcn_make_buffer_rsrc((void *)out, (short)0, (int)(n * 16u), 0x00020000);
+}
+
+__device__ __forceinline__ void store_rec(__amdgpu_buffer_rsrc_t out_rs, uint32_t pi, uint4 r)
+{
+	u32x4 v = { r.x, r.y, r.z, r.w };
+	__builtin_amdgcn_raw_buffer_store_b128(v, out_rs, pi * 16u, 0, 16);
 }
 
 // Make this wave's LDS writes visible to its own later LDS reads by other
@@ -2297,6 +2324,7 @@ __global__ __launch_bounds__(NW * WAVE, waves_per_eu(NW)) void mi_cls_kernel(KAr
 	// records are not held in registers through parse and classify.
 	const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
 		(void *)a.pkts, (short)0, (int)OOB_OFF, 0x00020000);
+	const __amdgpu_buffer_rsrc_t out_rs = rec_rsrc(a.out, a.n);   // the records (store_rec)
 	u32x4 d[NPIECE];
 	bool d_hi, hi_rows = true;
 	// window predictor: stage bytes 64..WIN-1 of long frames only while the
@@ -2379,7 +2407,7 @@ __global__ __launch_bounds__(NW * WAVE, waves_per_eu(NW)) void mi_cls_kernel(KAr
 		// previous tile's records: issued before this tile's prefetch, so the
 		// next wait for window data never waits behind a younger store
 		if (prev_valid)
-			store_rec(a.out + prev_pi, prev_rec);
+			store_rec(out_rs, prev_pi, prev_rec);
 		prev_valid = false;
 
 		// advance the pipeline: data of the next tile (nx), descriptors of the
@@ -2790,7 +2818,7 @@ __global__ __launch_bounds__(NW * WAVE, waves_per_eu(NW)) void mi_cls_kernel(KAr
 		prev_valid = valid;
 	}
 	if (prev_valid)
-		store_rec(a.out + prev_pi, prev_rec);
+		store_rec(out_rs, prev_pi, prev_rec);
 	// the waves of block 0 are the sample that sets the hint: stores to one
 	// address serialise, so never one per wave
 	if (saw_hi && a.hint && lane == 0 && blockIdx.x == 0)

@@ -87,9 +87,9 @@ PATCHES = {
 		}
 """),
         ("""	if (prev_valid)
-		store_rec(a.out + prev_pi, prev_rec);
+		store_rec(out_rs, prev_pi, prev_rec);
 	// the waves of block 0""", """	if (prev_valid)
-		store_rec(a.out + prev_pi, prev_rec);
+		store_rec(out_rs, prev_pi, prev_rec);
 	{
 		const uint64_t ts4 = __builtin_amdgcn_s_memrealtime();
 		const uint32_t t0 = blockIdx.x * NW + wave;
@@ -259,6 +259,25 @@ PATCHES["tsd"] = [
 			       (uint32_t)(q4 - q0), (uint32_t)(__builtin_amdgcn_s_memrealtime() - q0));
 	}"""),
 ]
+# The record store's cache policy (store_rec; profiles/r08_edges_ab.txt).
+# rec17: sc0 sc1 (auxiliary 17) instead of sc1.
+_WT = "	__builtin_amdgcn_raw_buffer_store_b128(v, out_rs, pi * 16u, 0, 16);\n"
+PATCHES["rec17"] = [(_WT, _WT.replace("0, 16)", "0, 17)"))]
+# rectail: written through only once the wave's tile queue is exhausted (the
+# records of its last two tiles: the ones still dirty in L2 when the launch
+# ends); the tiles before them stay nontemporal
+PATCHES["rectail"] = [
+    ("""		if (prev_valid)
+			store_rec(out_rs, prev_pi, prev_rec);
+		prev_valid = false;
+""", """		if (prev_valid) {
+			if (nx < nt)
+				store_rec(a.out + prev_pi, prev_rec);
+			else
+				store_rec(out_rs, prev_pi, prev_rec);
+		}
+		prev_valid = false;
+""")]
 DEFINES = {}
 
 
