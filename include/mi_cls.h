@@ -821,8 +821,9 @@ int mi_cls_rx_chain_submit(mi_cls_ctx_t *ctx, const uint8_t *pkts, size_t bytes,
  * include/odp_classification_internal.h:208-236 _odp_cls_enq: runs of equal
  * destination enqueued in arrival order), for a batch of any size and up to
  * MI_CLS_ENQ_DST_MAX destination queues.  No pools, no packet handles: every
- * enqueued record is delivered; allocation and the CoS pool switch stay with
- * the caller.  Per record, in arrival order:
+ * enqueued record is delivered.  The CoS pool switch and the frames it leaves
+ * without a packet are the pool plan's (mi_cls_pool_plan, below): plan its
+ * res_out.  Per record, in arrival order:
  *   in_errors    err != 0, or outcome MI_CLS_OUT_PARSE_DROP;
  *   in_discards  outcome MI_CLS_OUT_DISCARD or MI_CLS_OUT_LOOP;
  *   delivered    outcome MI_CLS_OUT_ENQ whose (cos, queue) the table maps:
@@ -1001,6 +1002,118 @@ int mi_cls_enq_runs_host_submit(mi_cls_ctx_t *ctx, const mi_cls_result_t *res_ho
 				mi_cls_run_t *runs_host, uint32_t run_cap, mi_cls_run_out_t *out_host,
 				uint64_t *ticket);
 int mi_cls_enq_runs_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
+
+/* ------------------------------------------------------------------------
+ * The pool plan: the first thing a pktio driver does with a classified
+ * packet, before it counts and enqueues it: the move into its CoS's pool
+ * (reference include/odp_packet_io_internal.h:352-371
+ * _odp_pktio_packet_to_pool, called at pktio/loop.c:332-337), for a batch of
+ * any size and up to MI_CLS_POOL_SLOTS pools.  A frame that gets no packet --
+ * its pool ran short, or it is longer than the pool's packets -- is freed and
+ * counted in in_discards by the reference and reaches no queue.  Per record i,
+ * in arrival order, with slot = cos_slot[cos]; the fates are tested in this
+ * order:
+ *   NONE      outcome is not MI_CLS_OUT_ENQ, or the CoS has no slot (cos_slot
+ *             0xFF or >= nslot: the enqueue plan's "stale"): takes no packet;
+ *   INPLACE   own[i] == slot + 1: the frame already sits in a packet of that
+ *             pool and stays there.  own is for loop-style drivers whose
+ *             frames are packets: own[i] is that packet's slot + 1, 0 for
+ *             none (a value above nslot selects nothing); own == NULL: no
+ *             frame has a packet (pcap frames).  An INPLACE frame is never
+ *             TOO_LONG: the reference compares the pools before it allocates;
+ *   TOO_LONG  len[i] > slot_cap[slot]: the allocation fails.  It takes no rank;
+ *   FRESH     rank < have[slot], where rank is the number of earlier records
+ *             of the slot that are FRESH or SHORT: takes packet base[slot] +
+ *             rank of the caller's array;
+ *   SHORT     rank >= have[slot]: the pool ran short.
+ * dec[i] = fate | slot << 4 (slot 0 for NONE).  idx[i] = base[slot] + rank for
+ * FRESH, 0xFFFFFFFF for every other fate: the caller keeps every packet it
+ * took in one array, slot k's at base[k] .. base[k] + have[k]; afterwards
+ * those from base[k] + used[k] on go back to the pool.  res_out[i] is res[i]
+ * with outcome replaced by MI_CLS_OUT_DISCARD for TOO_LONG and SHORT and no
+ * other byte changed, so the plans compose: mi_cls_enq_plan or
+ * mi_cls_enq_runs over res_out gives the deliveries, the free list and the
+ * counters of the reference's loop with the pool switch in it -- a loser is
+ * one more in_discards (loop.c:335), is in no queue group, run or vector, and
+ * keeps its in_errors count.  have[k] == 0xFFFFFFFF asks for the need alone:
+ * nothing is SHORT and the caller reads need[].
+ * This is the reference's packet-by-packet loop under "no packet returns to a
+ * pool during the batch", the assumption of the receive path's buckets too:
+ * frames of one pool get packets in arrival order, so a short pool leaves the
+ * same frames without one as frame-by-frame allocation from have[k] free
+ * packets would.
+ * Multi-GPU: there is no mi_cls_group_* form.  A shard's ranks start at zero,
+ * so the caller gives each shard its own have / base (its part of the packets).
+ * ---------------------------------------------------------------------- */
+#define MI_CLS_POOL_SLOTS 16
+/* The kernels' shape: a block of 16 waves walks a contiguous run of tiles of
+ * MI_CLS_POOL_TILE records; at most MI_CLS_POOL_GRID blocks (grid = min(
+ * MI_CLS_POOL_GRID, tiles); a batch of more tiles gives each block ceil(tiles /
+ * grid) of them). */
+#define MI_CLS_POOL_TILE 1024
+#define MI_CLS_POOL_GRID 256
+
+typedef struct mi_cls_pool_tab {
+	uint32_t nslot;                        /* slots in use, <= MI_CLS_POOL_SLOTS          */
+	uint32_t rsv;
+	uint32_t slot_cap[MI_CLS_POOL_SLOTS];  /* longest frame a packet of the slot can hold */
+	uint8_t  cos_slot[256];                /* CoS index -> slot; 0xFF: none               */
+	uint64_t stamp;                        /* as mi_cls_enq_tab_t.stamp                   */
+} mi_cls_pool_tab_t;
+
+#define MI_CLS_PF_NONE     0u  /* takes no packet: not MI_CLS_OUT_ENQ, or a CoS without a slot
+				  (cos_slot 0xFF or >= nslot: the enqueue plan's "stale")     */
+#define MI_CLS_PF_INPLACE  1u  /* own[i] == slot + 1: the packet stays where it is            */
+#define MI_CLS_PF_FRESH    2u  /* takes packet idx[i] of the caller's array                   */
+#define MI_CLS_PF_TOO_LONG 3u  /* len[i] > slot_cap[slot]: the allocation fails               */
+#define MI_CLS_PF_SHORT    4u  /* its rank >= have[slot]: the pool ran short                  */
+
+typedef struct mi_cls_pool_out {
+	uint64_t inplace, fresh, too_long, shorted;   /* records of each fate          */
+	uint32_t need[MI_CLS_POOL_SLOTS];              /* FRESH + SHORT of the slot     */
+	uint32_t used[MI_CLS_POOL_SLOTS];              /* FRESH = min(need, have)       */
+} mi_cls_pool_out_t;
+
+/* Plan the packets of n records in device memory.  res_dev / len_dev as for
+ * mi_cls_enq_plan (res_dev 16-byte aligned, as mi_cls_classify writes it);
+ * own_dev n bytes or NULL; res_out_dev n records (16-byte aligned; res_dev
+ * itself, in place, or an array disjoint from it), dec_dev and idx_dev n words,
+ * out_dev one mi_cls_pool_out_t (8-byte aligned): all written whole, no input
+ * value of theirs is read.  tab, have and base are host memory, read during
+ * the call.  The context needs no rules.  Stream-ordered on `stream`; returns
+ * after the launches are enqueued.  The scratch is the context's (of fixed
+ * size on this path; the staged host form's 9 B per record are grown by 1.5x
+ * and kept); a call on another stream than the previous pool plan's is ordered
+ * after it.  n == 0: out is zeroed (the arrays may be NULL).  -EINVAL: a NULL
+ * table, have, base, out or (n > 0) array other than own; tab->nslot >
+ * MI_CLS_POOL_SLOTS; n > MI_CLS_MAX_BATCH; base[k] + min(have[k], n) past
+ * 0xFFFFFFFE for a slot k < nslot; a misaligned res, res_out or out; a NULL
+ * context where there is a device.  -ENODEV: no device.
+ * mi_cls_last_launch: info[0] 256 + the waves per block (272), [1] the
+ * launches (3; 1 for n == 0), [2]-[5] 0, [6] the grid. */
+int mi_cls_pool_plan(mi_cls_ctx_t *ctx, const mi_cls_result_t *res_dev, const uint16_t *len_dev,
+		     const uint8_t *own_dev /* may be NULL */, uint32_t n,
+		     const mi_cls_pool_tab_t *tab,
+		     const uint32_t have[MI_CLS_POOL_SLOTS], const uint32_t base[MI_CLS_POOL_SLOTS],
+		     mi_cls_result_t *res_out_dev, uint32_t *dec_dev, uint32_t *idx_dev,
+		     mi_cls_pool_out_t *out_dev, void *stream);
+
+/* Host-memory batch, as mi_cls_enq_plan_host and its submit / wait forms:
+ * res, len, own (if given), res_out, dec, idx and out all page-locked: read
+ * and written in place; otherwise the records, lengths and own go through the
+ * context's staging buffers and res_out, dec, idx and out are copied back. */
+int mi_cls_pool_plan_host(mi_cls_ctx_t *ctx, const mi_cls_result_t *res_host, const uint16_t *len_host,
+			  const uint8_t *own_host, uint32_t n, const mi_cls_pool_tab_t *tab,
+			  const uint32_t have[MI_CLS_POOL_SLOTS], const uint32_t base[MI_CLS_POOL_SLOTS],
+			  mi_cls_result_t *res_out_host, uint32_t *dec_host, uint32_t *idx_host,
+			  mi_cls_pool_out_t *out_host);
+int mi_cls_pool_plan_host_submit(mi_cls_ctx_t *ctx, const mi_cls_result_t *res_host,
+				 const uint16_t *len_host, const uint8_t *own_host, uint32_t n,
+				 const mi_cls_pool_tab_t *tab, const uint32_t have[MI_CLS_POOL_SLOTS],
+				 const uint32_t base[MI_CLS_POOL_SLOTS], mi_cls_result_t *res_out_host,
+				 uint32_t *dec_host, uint32_t *idx_host, mi_cls_pool_out_t *out_host,
+				 uint64_t *ticket);
+int mi_cls_pool_plan_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
 
 /* 1 if p lies in page-locked host memory that the device addresses at the
  * same address (the receive delivery's requirement), else 0. */

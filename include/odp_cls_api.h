@@ -459,6 +459,52 @@ int odp_amd_cls_enq_runs_host_submit(odp_pktio_t pktio, const void *res, const u
 				     uint64_t *ticket);
 int odp_amd_cls_enq_runs_host_wait(odp_pktio_t pktio, uint64_t ticket);
 
+/* The pool plan's table of the current control plane for a pktio
+ * (mi_cls_pool_tab_t, mi_cls.h), built on the host (no device needed): slot 0
+ * is the pktio's pool; each valid CoS whose action is ENQUEUE maps to the slot
+ * of its odp_cls_cos_pool, or to slot 0 when it has none (the reference falls
+ * back to the pktio's pool); further slots count up in order of first
+ * appearance scanning CoS index; DROP and invalid CoS have no slot (0xFF).
+ * slot_cap[k] is the data capacity of a packet of pool k.  pools[slot] (room
+ * for MI_CLS_POOL_SLOTS = 16): each slot's pool; *nslot: slots in use; *gen:
+ * the generation the table was built under.  0, -EINVAL (a NULL argument, no
+ * such pktio, a slot's pool that is no packet pool), or -E2BIG past 16 pools.
+ * odp_amd_cls_pooltab_cos is its control-plane half for a caller with pools of
+ * its own: it leaves slot_cap zero. */
+struct mi_cls_pool_tab;
+struct mi_cls_pool_out;
+int odp_amd_cls_pooltab_fill(odp_pktio_t pktio, struct mi_cls_pool_tab *tab, odp_pool_t pools[],
+			     uint32_t *nslot, uint64_t *gen);
+int odp_amd_cls_pooltab_cos(odp_pool_t pktio_pool, struct mi_cls_pool_tab *tab, odp_pool_t pools[],
+			    uint32_t *nslot, uint64_t *gen);
+
+/* own[i] for the pool plan, on the host: the slot + 1 of packet pk[i]'s pool
+ * (odp_packet_pool) among pools[0 .. nslot), 0 when it is none of them or the
+ * handle is ODP_PACKET_INVALID.  0 or -EINVAL. */
+int odp_amd_cls_pool_own(const odp_packet_t pk[], uint32_t n, const odp_pool_t pools[], uint32_t nslot,
+			 uint8_t own[]);
+
+/* The pool plan of a classified batch on the pktio's context (mi_cls_pool_plan
+ * and its host forms): which records take a packet of their CoS's pool and
+ * which one, which get none and become discards in res_out -- plan res_out with
+ * odp_amd_cls_enq_plan or odp_amd_cls_enq_runs.  -ENOTSUP on pktios over
+ * several GPUs, as the enqueue plan: a shard's ranks start at zero, so plan
+ * each shard on its device with its own have / base. */
+int odp_amd_cls_pool_plan(odp_pktio_t pktio, const void *res_dev, const uint16_t *len_dev,
+			  const uint8_t *own_dev, uint32_t n, const struct mi_cls_pool_tab *tab,
+			  const uint32_t have[], const uint32_t base[], void *res_out_dev, uint32_t *dec_dev,
+			  uint32_t *idx_dev, struct mi_cls_pool_out *out_dev, void *stream);
+int odp_amd_cls_pool_plan_host(odp_pktio_t pktio, const void *res, const uint16_t *len, const uint8_t *own,
+			       uint32_t n, const struct mi_cls_pool_tab *tab, const uint32_t have[],
+			       const uint32_t base[], void *res_out, uint32_t *dec, uint32_t *idx,
+			       struct mi_cls_pool_out *out);
+int odp_amd_cls_pool_plan_host_submit(odp_pktio_t pktio, const void *res, const uint16_t *len,
+				      const uint8_t *own, uint32_t n, const struct mi_cls_pool_tab *tab,
+				      const uint32_t have[], const uint32_t base[], void *res_out,
+				      uint32_t *dec, uint32_t *idx, struct mi_cls_pool_out *out,
+				      uint64_t *ticket);
+int odp_amd_cls_pool_plan_host_wait(odp_pktio_t pktio, uint64_t ticket);
+
 /* Device contexts of the pktio (its GPUs, ODP_AMD_GPUS / create_multi); 1
  * for a single-device pktio, < 0 on error. */
 int odp_amd_cls_devices(odp_pktio_t pktio);

@@ -80,12 +80,12 @@ def build(force: bool = False, out_dir: str = PKG, defines=(), src_dir: str = SR
     host_deps = [asm_src, spec_src, prog_hdr, os.path.join(SRC, "mi_cls_asm.h"),
                  os.path.join(SRC, "mi_cls_spec.h")]
     k_srcs = [os.path.join(SRC, f"mi_cls_k{w}.hip") for w in (4, 8, 12, 16, "f", "f12", "f16", "c4",
-                                                              "c16", "d", "t", "h", "p", "l", "q", "r")]
+                                                              "c16", "d", "t", "h", "p", "l", "q", "r", "a")]
     tx_hdr = os.path.join(SRC, "mi_cls_tx_dev.h")
     parse_hdr = os.path.join(SRC, "mi_cls_parse_dev.h")
     lso_hdr = os.path.join(SRC, "mi_cls_lso_dev.h")
     enq_hdrs = [os.path.join(SRC, "mi_cls_enq_dev.h"), os.path.join(SRC, "mi_cls_rank_dev.h"),
-                os.path.join(SRC, "mi_cls_run_dev.h")]
+                os.path.join(SRC, "mi_cls_run_dev.h"), os.path.join(SRC, "mi_cls_pool_dev.h")]
     variant = bool(defines) or src_dir != globals()["SRC"]
     if force or variant or _stale(mi_so, [mi_src, mi_hdr, tx_hdr, parse_hdr, lso_hdr] + enq_hdrs + host_deps + k_srcs + hdrs + [__file__]):
         # one translation unit per block shape + the host code, compiled in
@@ -172,7 +172,7 @@ def build_test_drivers(force: bool = False):
     deps = [os.path.join(PKG, "libodp_cls.so"), os.path.join(PKG, "libodph.so"),
             os.path.join(INC, "odp_rt.h"), os.path.join(INC, "odp", "helper", "odph_api.h")]
     for name in ("rx_driver", "rt_unit", "tx_driver", "parse_driver", "lso_driver", "mq_driver",
-                 "runtab_driver"):
+                 "runtab_driver", "pooltab_driver"):
         src = os.path.join(ROOT, "tests", "rt", name + ".c")
         if not os.path.exists(src):
             continue

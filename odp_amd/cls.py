@@ -176,6 +176,67 @@ def run_tab(mode, vmax, vslot) -> RunTab:
     return t
 
 
+# the pool plan (include/mi_cls.h): the slots, the fates of dec, the kernels'
+# shape
+POOL_SLOTS = 16
+POOL_TILE, POOL_GRID = 1024, 256
+POOL_NONE, POOL_INPLACE, POOL_FRESH, POOL_TOO_LONG, POOL_SHORT = 0, 1, 2, 3, 4
+POOL_NO_IDX = 0xFFFFFFFF        # idx of every record that is not FRESH
+POOL_UNLIMITED = 0xFFFFFFFF     # have[k]: the need alone, nothing is SHORT
+
+
+class PoolTab(C.Structure):
+    """mi_cls_pool_tab_t."""
+    _fields_ = [("nslot", C.c_uint32), ("rsv", C.c_uint32), ("slot_cap", C.c_uint32 * POOL_SLOTS),
+                ("cos_slot", C.c_uint8 * 256), ("stamp", C.c_uint64)]
+
+
+class PoolOut(C.Structure):
+    """mi_cls_pool_out_t."""
+    _fields_ = [("inplace", C.c_uint64), ("fresh", C.c_uint64), ("too_long", C.c_uint64),
+                ("shorted", C.c_uint64), ("need", C.c_uint32 * POOL_SLOTS), ("used", C.c_uint32 * POOL_SLOTS)]
+
+
+POOL_OUT_FIELDS = ("inplace", "fresh", "too_long", "shorted")
+POOL_OUT_WORDS = C.sizeof(PoolOut) // 4      # 32-bit words
+POOL_OUT_DTYPE = np.dtype([("inplace", "<u8"), ("fresh", "<u8"), ("too_long", "<u8"), ("shorted", "<u8"),
+                           ("need", "<u4", (POOL_SLOTS,)), ("used", "<u4", (POOL_SLOTS,))])
+
+
+def pool_tab(cos_slot, slot_cap, nslot=None) -> PoolTab:
+    """A mi_cls_pool_tab_t from its arrays (cos_slot: up to 256 values by CoS
+    index, the rest 0xFF; slot_cap: up to POOL_SLOTS values; nslot: their number
+    by default), with a stamp no earlier table of this process had."""
+    global _enq_stamps
+    t = PoolTab()
+    cs = np.ctypeslib.as_array(t.cos_slot)
+    cs[:] = 0xFF
+    s = np.asarray(cos_slot)
+    cs[:s.shape[0]] = s
+    caps = np.asarray(slot_cap, dtype=np.uint32)
+    np.ctypeslib.as_array(t.slot_cap)[:caps.shape[0]] = caps
+    t.nslot = int(caps.shape[0] if nslot is None else nslot)
+    _enq_stamps += 1
+    t.stamp = (1 << 32) + _enq_stamps
+    return t
+
+
+def pool_out_dict(words32):
+    """The 40 32-bit words of a mi_cls_pool_out_t as a dict (need, used: lists)."""
+    o = np.ascontiguousarray(words32, dtype=np.uint32).view(POOL_OUT_DTYPE)[0]
+    d = {k: int(o[k]) for k in POOL_OUT_FIELDS}
+    d["need"] = [int(v) for v in o["need"]]
+    d["used"] = [int(v) for v in o["used"]]
+    return d
+
+
+def _pool_u32x16(v):
+    a = (C.c_uint32 * POOL_SLOTS)()
+    for k, x in enumerate(v):
+        a[k] = int(x)
+    return a
+
+
 def run_out_dict(words):
     """The 24 uint64 of a mi_cls_run_out_t as a dict (vec_need: a list)."""
     w = [int(v) for v in words]
@@ -296,6 +357,18 @@ def _load():
         "odp_amd_cls_enq_runs_host_submit": (i32, [vp, vp, vp, u32, C.POINTER(EnqTab), C.POINTER(RunTab), u32, vp,
                                                    vp, u32, vp, C.POINTER(C.c_uint64)]),
         "odp_amd_cls_enq_runs_host_wait": (i32, [vp, C.c_uint64]),
+        "mi_cls_pool_plan": (i32, [vp, vp, vp, vp, u32, C.POINTER(PoolTab), vp, vp, vp, vp, vp, vp, vp]),
+        "mi_cls_pool_plan_host": (i32, [vp, vp, vp, vp, u32, C.POINTER(PoolTab), vp, vp, vp, vp, vp, vp]),
+        "mi_cls_pool_plan_host_submit": (i32, [vp, vp, vp, vp, u32, C.POINTER(PoolTab), vp, vp, vp, vp, vp, vp,
+                                               C.POINTER(C.c_uint64)]),
+        "mi_cls_pool_plan_host_wait": (i32, [vp, C.c_uint64]),
+        "odp_amd_cls_pooltab_cos": (i32, [vp, C.POINTER(PoolTab), C.POINTER(vp), C.POINTER(u32),
+                                          C.POINTER(C.c_uint64)]),
+        "odp_amd_cls_pool_plan": (i32, [vp, vp, vp, vp, u32, C.POINTER(PoolTab), vp, vp, vp, vp, vp, vp, vp]),
+        "odp_amd_cls_pool_plan_host": (i32, [vp, vp, vp, vp, u32, C.POINTER(PoolTab), vp, vp, vp, vp, vp, vp]),
+        "odp_amd_cls_pool_plan_host_submit": (i32, [vp, vp, vp, vp, u32, C.POINTER(PoolTab), vp, vp, vp, vp, vp,
+                                                    vp, C.POINTER(C.c_uint64)]),
+        "odp_amd_cls_pool_plan_host_wait": (i32, [vp, C.c_uint64]),
         "odp_amd_cls_parse_host": (i32, [vp, C.c_size_t, vp, vp, u32, u32, u32, u32, vp]),
         "odp_amd_cls_parse_term": (None, []),
     }
@@ -659,6 +732,76 @@ def _enq_runs_host(L, prefix, handle, res, ln, tab, rtab, burst, seq, runs, out,
         raise RuntimeError(f"{prefix}: {rc}")
 
 
+def _pool_plan_device(call, handle, records, lens, own, tab, have, base, device, poison=0xA5A5A5A5,
+                      in_place=False):
+    """Upload records, lens and own (None: NULL), run the device form `call`
+    (mi_cls_pool_plan / odp_amd_cls_pool_plan) on torch's current stream and
+    return (res_out, dec, idx, out): res_out as rules.RESULT_DTYPE, out the dict
+    of pool_out_dict.  Every output word, and a guard past each array, holds
+    `poison` before the launch.  in_place: res_out is the uploaded records' own
+    array (a guard record follows it)."""
+    import torch
+    dev = torch.device(device)
+    rec = np.ascontiguousarray(records, dtype=R.RESULT_DTYPE)
+    n = int(rec.shape[0])
+    ln = np.ascontiguousarray(lens, dtype=np.uint16)
+    assert ln.shape[0] == n
+    up = np.full(4 * (n + 1), poison, np.uint32)
+    up[:4 * n] = rec.view(np.uint32).reshape(-1)
+    t_res = torch.from_numpy(up.view(np.int32)).to(dev)
+    t_len = torch.from_numpy(ln.view(np.int16).copy() if n else np.zeros(1, np.int16)).to(dev)
+    t_own = None
+    if own is not None:
+        ow = np.ascontiguousarray(own, dtype=np.uint8)
+        assert ow.shape[0] == n
+        t_own = torch.from_numpy(ow.copy() if n else np.zeros(1, np.uint8)).to(dev)
+    t_ro = t_res if in_place else torch.from_numpy(np.full(4 * (n + 1), poison, np.uint32).view(np.int32)).to(dev)
+    t_dec = torch.from_numpy(np.full(n + 1, poison, np.uint32).view(np.int32)).to(dev)
+    t_idx = torch.from_numpy(np.full(n + 1, poison, np.uint32).view(np.int32)).to(dev)
+    t_out = torch.from_numpy(np.full(POOL_OUT_WORDS + 2, poison, np.uint32).view(np.int32)).to(dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    h, b = _pool_u32x16(have), _pool_u32x16(base)
+    rc = call(handle, t_res.data_ptr(), t_len.data_ptr(), t_own.data_ptr() if t_own is not None else None, n,
+              C.byref(tab), h, b, t_ro.data_ptr(), t_dec.data_ptr(), t_idx.data_ptr(), t_out.data_ptr(),
+              stream or None)
+    if rc != 0:
+        raise RuntimeError(f"pool_plan: {rc} ({lib().mi_cls_strerror(rc).decode()})")
+    torch.cuda.synchronize(dev)
+    ro = t_ro.cpu().numpy().view(np.uint32)
+    dec = t_dec.cpu().numpy().view(np.uint32)
+    idx = t_idx.cpu().numpy().view(np.uint32)
+    out = t_out.cpu().numpy().view(np.uint32)
+    if np.any(ro[4 * n:] != poison) or dec[n] != poison or idx[n] != poison or np.any(out[-2:] != poison):
+        raise RuntimeError("pool_plan wrote past an output array")
+    if not in_place and not np.array_equal(t_res.cpu().numpy().view(np.uint32), up):
+        raise RuntimeError("pool_plan wrote its input records")
+    return ro[:4 * n].copy().view(R.RESULT_DTYPE), dec[:n].copy(), idx[:n].copy(), pool_out_dict(out[:-2])
+
+
+def _pool_plan_host(L, prefix, handle, res, ln, own, tab, have, base, res_out, dec, idx, out, submit):
+    """The host forms of `prefix` (mi_cls_pool_plan_host /
+    odp_amd_cls_pool_plan_host) on numpy arrays, as _enq_plan_host.  own: None
+    for NULL; out: POOL_OUT_DTYPE (one element) or its 40 uint32.  submit: the
+    _submit / _wait pair; "ticket": the _submit alone, returning the ticket."""
+    n = int(res.shape[0])
+    args = (handle, res.ctypes.data if n else None, ln.ctypes.data if n else None,
+            own.ctypes.data if n and own is not None else None, n, C.byref(tab), _pool_u32x16(have),
+            _pool_u32x16(base), res_out.ctypes.data if n else None, dec.ctypes.data if n else None,
+            idx.ctypes.data if n else None, out.ctypes.data)
+    if submit:
+        t = C.c_uint64()
+        rc = getattr(L, prefix + "_submit")(*args, C.byref(t))
+        if rc == 0 and submit == "ticket":
+            return t.value
+        if rc == 0:
+            rc = getattr(L, prefix + "_wait")(handle, t.value)
+    else:
+        rc = getattr(L, prefix)(*args)
+    if rc != 0:
+        raise RuntimeError(f"{prefix}: {rc}")
+    return None
+
+
 class EnqContext(_FeatureContext):
     """A device context for the enqueue plan (mi_cls_enq_plan and its host
     entries: a classified batch's records grouped by destination queue, the
@@ -684,6 +827,30 @@ class EnqContext(_FeatureContext):
         """mi_cls_enq_runs_host (submit: _host_submit / _host_wait)."""
         _enq_runs_host(self.L, "mi_cls_enq_runs_host", self.ctx, res, ln, tab, rtab, burst, seq, runs, out,
                        submit)
+
+    def pools_device(self, d_res, d_len, d_own, n, tab, have, base, d_res_out, d_dec, d_idx, d_out, stream=0):
+        """mi_cls_pool_plan on device pointers (ints), stream-ordered.  Returns
+        the C status."""
+        return self.L.mi_cls_pool_plan(self.ctx, d_res or None, d_len or None, d_own or None, n, C.byref(tab),
+                                       _pool_u32x16(have), _pool_u32x16(base), d_res_out or None,
+                                       d_dec or None, d_idx or None, d_out or None, stream or None)
+
+    def pools(self, records, lens, own, tab, have, base, poison=0xA5A5A5A5, in_place=False):
+        """Upload records, lens and own (None: no frame has a packet), plan the
+        pools (mi_cls_pool_plan); returns (res_out, dec, idx, out)."""
+        return _pool_plan_device(self.L.mi_cls_pool_plan, self.ctx, records, lens, own, tab, have, base,
+                                 f"cuda:{self.gpu}", poison, in_place)
+
+    def pools_host(self, res, ln, own, tab, have, base, res_out, dec, idx, out, submit=False):
+        """mi_cls_pool_plan_host (submit: _host_submit / _host_wait; "ticket":
+        _host_submit alone, returns the ticket for pools_wait)."""
+        return _pool_plan_host(self.L, "mi_cls_pool_plan_host", self.ctx, res, ln, own, tab, have, base, res_out,
+                               dec, idx, out, submit)
+
+    def pools_wait(self, ticket):
+        rc = self.L.mi_cls_pool_plan_host_wait(self.ctx, ticket)
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_pool_plan_host_wait: {rc}")
 
     def plan_device(self, d_res, d_len, n, tab, d_perm, d_gbeg, d_out, stream=0):
         """On device pointers (ints), stream-ordered.  Returns the C status."""
@@ -1042,6 +1209,37 @@ class Classifier:
             rtab = self.run_table()[0]
         _enq_runs_host(self.L, "odp_amd_cls_enq_runs_host", self.pktio, res, ln, tab, rtab, burst, seq, runs, out,
                        submit)
+
+    def pool_table(self, slot_cap, pktio_pool=None):
+        """The pool plan's table of the current control plane
+        (odp_amd_cls_pooltab_cos; host only) for a pktio whose own pool is
+        pktio_pool.  slot_cap: {pool handle: capacity}, or one capacity for
+        every slot.  Returns (PoolTab, pools, gen): pools[slot] each slot's
+        pool handle."""
+        tab = PoolTab()
+        p = (C.c_void_p * POOL_SLOTS)()
+        ns, gen = C.c_uint32(), C.c_uint64()
+        rc = self.L.odp_amd_cls_pooltab_cos(pktio_pool, C.byref(tab), p, C.byref(ns), C.byref(gen))
+        if rc != 0:
+            raise RuntimeError(f"odp_amd_cls_pooltab_cos: {rc}")
+        pools = [_h(p[i]) for i in range(ns.value)]
+        for k, h in enumerate(pools):
+            tab.slot_cap[k] = int(slot_cap[h] if isinstance(slot_cap, dict) else slot_cap)
+        return tab, pools, gen.value
+
+    def pool_plan(self, records, lens, own, have, base, tab, device="cuda:0", poison=0xA5A5A5A5,
+                  in_place=False):
+        """The pool plan of classified records (odp_amd_cls_pool_plan, on the
+        pktio's context and torch's current stream): returns (res_out, dec,
+        idx, out).  tab: pool_table()'s."""
+        return _pool_plan_device(self.L.odp_amd_cls_pool_plan, self.pktio, records, lens, own, tab, have, base,
+                                 device, poison, in_place)
+
+    def pool_plan_host(self, res, ln, own, have, base, res_out, dec, idx, out, tab, submit=False):
+        """odp_amd_cls_pool_plan_host on numpy arrays (submit: the _submit /
+        _wait pair), as EnqContext.pools_host."""
+        return _pool_plan_host(self.L, "odp_amd_cls_pool_plan_host", self.pktio, res, ln, own, tab, have, base,
+                               res_out, dec, idx, out, submit)
 
     def cos_stats_packets(self, cos_handle):
         s = CosStats()

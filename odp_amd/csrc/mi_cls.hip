@@ -79,6 +79,17 @@ struct mi_cls_ctx {
 	hipEvent_t run_ev = nullptr;
 	hipStream_t run_last = nullptr;
 	bool run_used = false;
+	// the pool plan (mi_cls_pool_plan), likewise: the scratch of fixed size, the
+	// staged form's own, dec and idx (pool_st_cap records), the table's snapshot
+	// and whose copy the device holds
+	uint8_t *d_pool_fix = nullptr, *d_pool_st = nullptr;
+	size_t pool_st_cap = 0;
+	mi_cls_pool_tab_t *h_pool_tab = nullptr;
+	const void *pool_tab_src = nullptr;
+	uint64_t pool_tab_stamp = 0;
+	hipEvent_t pool_ev = nullptr;
+	hipStream_t pool_last = nullptr;
+	bool pool_used = false;
 	// program-specialised flat kernel for the loaded program (null: none)
 	std::shared_ptr<SpecCode> spec;
 	uint32_t batch_hint = 0; // largest batch per call (mi_cls_batch_hint), 0: unknown
@@ -168,6 +179,7 @@ static int preload_kernels(int device)
 	chk(mi_cls_launch_lso(0, nullptr, LsoArgs{}));
 	chk(mi_cls_launch_enq(nullptr, EnqArgs{}, 0, true));
 	chk(mi_cls_launch_run(nullptr, RunArgs{}, true));
+	chk(mi_cls_launch_pool(nullptr, PoolArgs{}, true));
 	if (bad)
 		return bad;
 	done.insert(device);
@@ -270,6 +282,14 @@ extern "C" int mi_cls_ctx_destroy(mi_cls_ctx_t *c)
 	(void)hipFree(c->d_run_st);
 	if (c->h_run_tab)
 		(void)hipHostFree(c->h_run_tab);
+	if (c->pool_ev) {
+		(void)hipEventSynchronize(c->pool_ev);
+		(void)hipEventDestroy(c->pool_ev);
+	}
+	(void)hipFree(c->d_pool_fix);
+	(void)hipFree(c->d_pool_st);
+	if (c->h_pool_tab)
+		(void)hipHostFree(c->h_pool_tab);
 	(void)hipFree(c->d_rx);
 	if (c->h_tab)
 		(void)hipHostFree(c->h_tab);
@@ -1833,6 +1853,223 @@ extern "C" int mi_cls_enq_runs_host_submit(mi_cls_ctx_t *c, const mi_cls_result_
 }
 
 extern "C" int mi_cls_enq_runs_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
+{
+	return feature_host_wait(c, ticket);
+}
+
+// -------------------------------------------------------------- the pool plan
+// The pool plan's scratch in the context, by the enqueue plan's policy.  Of
+// fixed size: the table's device copy, the count matrix (slot-major), the two
+// counters and the staged form's out.  The device path needs nothing per
+// record; the staged host form keeps own (1 B), dec and idx (4 B each) per
+// record in a buffer of its own, and its res_out in the staged records' place.
+#define POOL_FIX_TAB 0u
+#define POOL_FIX_CNT (POOL_FIX_TAB + ENQ_ALIGN(sizeof(mi_cls_pool_tab_t)))
+#define POOL_FIX_CTR (POOL_FIX_CNT + ENQ_ALIGN((size_t)MI_CLS_POOL_SLOTS * MI_CLS_POOL_GRID * 4u))
+#define POOL_FIX_OUT (POOL_FIX_CTR + ENQ_ALIGN(16u))
+#define POOL_FIX_BYTES (POOL_FIX_OUT + ENQ_ALIGN(sizeof(mi_cls_pool_out_t)))
+
+static uint32_t *pool_st_dec(const mi_cls_ctx_t *c) { return (uint32_t *)c->d_pool_st; }
+static uint32_t *pool_st_idx(const mi_cls_ctx_t *c) { return (uint32_t *)(c->d_pool_st + ENQ_ALIGN(4u * c->pool_st_cap)); }
+static uint8_t *pool_st_own(const mi_cls_ctx_t *c) { return c->d_pool_st + 2u * ENQ_ALIGN(4u * c->pool_st_cap); }
+
+// Before the scratch is replaced, and before the table's snapshot or device
+// copy is rewritten, the previous pool plan has ended (pool_ev).
+static int pool_idle(mi_cls_ctx_t *c)
+{
+	if (c->pool_used)
+		HIP_OK(hipEventSynchronize(c->pool_ev));
+	return 0;
+}
+
+// staged: records of the staged host form (0: the device path)
+static int pool_scratch(mi_cls_ctx_t *c, uint32_t staged)
+{
+	if (!c->d_pool_fix) {
+		if (!c->pool_ev && hipEventCreateWithFlags(&c->pool_ev, hipEventDisableTiming) != hipSuccess)
+			return -EIO;
+		if ((!c->h_pool_tab &&
+		     hipHostMalloc((void **)&c->h_pool_tab, sizeof(mi_cls_pool_tab_t), hipHostMallocDefault) != hipSuccess) ||
+		    hipMalloc((void **)&c->d_pool_fix, POOL_FIX_BYTES) != hipSuccess)
+			return -ENOMEM;
+	}
+	if (staged > c->pool_st_cap) {
+		const int rc = pool_idle(c);
+		if (rc)
+			return rc;
+		(void)hipFree(c->d_pool_st);
+		c->d_pool_st = nullptr;
+		c->pool_st_cap = 0;
+		const size_t cap = staged < 4096u ? 4096u : (size_t)staged + staged / 2;
+		if (hipMalloc((void **)&c->d_pool_st, 2u * ENQ_ALIGN(4u * cap) + ENQ_ALIGN(cap)) != hipSuccess)
+			return -ENOMEM;
+		c->pool_st_cap = cap;
+	}
+	return 0;
+}
+
+// The table and the packets first (host memory, no device needed), then the
+// context, then the batch
+static int pool_check(const mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len, uint32_t n,
+		      const mi_cls_pool_tab_t *tab, const uint32_t *have, const uint32_t *base,
+		      const mi_cls_result_t *res_out, const uint32_t *dec, const uint32_t *idx,
+		      const mi_cls_pool_out_t *out)
+{
+	if (!tab || !have || !base || tab->nslot > MI_CLS_POOL_SLOTS || n > MI_CLS_MAX_BATCH)
+		return -EINVAL;
+	// an index stays below 0xFFFFFFFF, the value of "no packet"
+	for (uint32_t k = 0; k < tab->nslot; ++k)
+		if ((uint64_t)base[k] + (have[k] < n ? have[k] : n) > 0xFFFFFFFEull)
+			return -EINVAL;
+	if (!c)
+		return no_ctx();
+	if (!out || ((uintptr_t)out & 7u) != 0)
+		return -EINVAL;
+	if (n == 0)
+		return 0;
+	return res && len && res_out && dec && idx && (((uintptr_t)res | (uintptr_t)res_out) & 15u) == 0 ? 0 : -EINVAL;
+}
+
+extern "C" int mi_cls_pool_plan(mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len,
+				const uint8_t *own, uint32_t n, const mi_cls_pool_tab_t *tab,
+				const uint32_t *have, const uint32_t *base, mi_cls_result_t *res_out, uint32_t *dec,
+				uint32_t *idx, mi_cls_pool_out_t *out, void *stream)
+{
+	int rc = pool_check(c, res, len, n, tab, have, base, res_out, dec, idx, out);
+	if (rc)
+		return rc;
+	hipStream_t st = (hipStream_t)stream;
+	HIP_OK(set_device(c->device));
+	rc = pool_scratch(c, 0);
+	if (rc)
+		return rc;
+	// the scratch is one plan's at a time: a plan on another stream follows
+	// the previous one
+	if (c->pool_used && c->pool_last != st)
+		HIP_OK(hipStreamWaitEvent(st, c->pool_ev, 0));
+	// the table's device copy, refreshed when the host table's stamp moved
+	mi_cls_pool_tab_t *dtab = (mi_cls_pool_tab_t *)(c->d_pool_fix + POOL_FIX_TAB);
+	const uint32_t nslot = tab->nslot;
+	if (!c->pool_tab_src || c->pool_tab_src != tab || c->pool_tab_stamp != tab->stamp) {
+		rc = pool_idle(c);
+		if (rc)
+			return rc;
+		memcpy(c->h_pool_tab, tab, sizeof(*tab));
+		c->pool_tab_src = nullptr;
+		HIP_OK(hipMemcpyAsync(dtab, c->h_pool_tab, sizeof(*tab), hipMemcpyHostToDevice, st));
+		c->pool_tab_src = tab;
+		c->pool_tab_stamp = c->h_pool_tab->stamp;
+	}
+	PoolArgs a;
+	memset(&a, 0, sizeof(a));
+	a.res = res;
+	a.len = len;
+	a.own = own;
+	a.tab = dtab;
+	a.n = n;
+	a.nslot = nslot;
+	const uint64_t tiles = ((uint64_t)n + MI_CLS_POOL_TILE - 1u) / MI_CLS_POOL_TILE;
+	a.grid = (uint32_t)(tiles < MI_CLS_POOL_GRID ? tiles : MI_CLS_POOL_GRID);
+	a.tpb = a.grid ? (uint32_t)((tiles + a.grid - 1u) / a.grid) : 0u;
+	for (uint32_t k = 0; k < MI_CLS_POOL_SLOTS; ++k) {
+		a.have[k] = k < nslot ? have[k] : 0u;
+		a.base[k] = k < nslot ? base[k] : 0u;
+	}
+	a.cnt = (uint32_t *)(c->d_pool_fix + POOL_FIX_CNT);
+	a.ctr = (unsigned long long *)(c->d_pool_fix + POOL_FIX_CTR);
+	a.res_out = res_out;
+	a.dec = dec;
+	a.idx = idx;
+	a.out = out;
+	// this call's counters start from zero, whatever the last one left
+	HIP_OK(hipMemsetAsync(a.ctr, 0, 16u, st));
+	uint32_t *last = c->last;
+	last[0] = 256u + MI_CLS_POOL_TILE / WAVE;
+	last[1] = n ? 3u : 1u;
+	last[2] = last[3] = last[4] = last[5] = 0;
+	last[6] = a.grid;
+	rc = mi_cls_launch_pool(st, a, false);
+	if (rc)
+		return rc;
+	HIP_OK(hipEventRecord(c->pool_ev, st));
+	c->pool_used = true;
+	c->pool_last = st;
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+// A host batch on the context's stream, nothing waited for: in place when
+// every array is page-locked, else the records and lengths through the
+// staging buffers (res_out takes the staged records' place), own, dec and idx
+// through the plan's staging buffer and out through the scratch.
+static int pool_host_launch(mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len, const uint8_t *own,
+			    uint32_t n, const mi_cls_pool_tab_t *tab, const uint32_t *have, const uint32_t *base,
+			    mi_cls_result_t *res_out, uint32_t *dec, uint32_t *idx, mi_cls_pool_out_t *out)
+{
+	HIP_OK(set_device(c->device));
+	const mi_cls_result_t *zr = res;
+	const uint16_t *zl = len;
+	const uint8_t *zw = own;
+	mi_cls_result_t *zq = res_out;
+	uint32_t *zd = dec, *zi = idx;
+	mi_cls_pool_out_t *zo = out;
+	if (dev_views(zo) && (n == 0 || (dev_views(zr, zl, zq, zd, zi) && (!own || dev_views(zw)))))
+		return mi_cls_pool_plan(c, zr, zl, n ? zw : nullptr, n, tab, have, base, zq, zd, zi, zo, c->stream);
+	int rc = stage_bufs(c, 0, n);
+	if (!rc)
+		rc = pool_scratch(c, n ? n : 1u);
+	if (rc)
+		return rc;
+	uint8_t *down = own && n ? pool_st_own(c) : nullptr;
+	mi_cls_pool_out_t *dout = (mi_cls_pool_out_t *)(c->d_pool_fix + POOL_FIX_OUT);
+	if (n) {
+		HIP_OK(hipMemcpyAsync(c->d_out, res, n * sizeof(mi_cls_result_t), hipMemcpyHostToDevice, c->stream));
+		HIP_OK(hipMemcpyAsync(c->d_len, len, n * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+		if (down)
+			HIP_OK(hipMemcpyAsync(down, own, n, hipMemcpyHostToDevice, c->stream));
+	}
+	rc = mi_cls_pool_plan(c, c->d_out, c->d_len, down, n, tab, have, base, c->d_out, pool_st_dec(c),
+			      pool_st_idx(c), dout, c->stream);
+	if (rc)
+		return rc;
+	if (n) {
+		HIP_OK(hipMemcpyAsync(res_out, c->d_out, n * sizeof(mi_cls_result_t), hipMemcpyDeviceToHost, c->stream));
+		HIP_OK(hipMemcpyAsync(dec, pool_st_dec(c), n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+		HIP_OK(hipMemcpyAsync(idx, pool_st_idx(c), n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	}
+	HIP_OK(hipMemcpyAsync(out, dout, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+	// the scratch is this plan's until the copies have read it
+	HIP_OK(hipEventRecord(c->pool_ev, c->stream));
+	return 0;
+}
+
+extern "C" int mi_cls_pool_plan_host(mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len,
+				     const uint8_t *own, uint32_t n, const mi_cls_pool_tab_t *tab,
+				     const uint32_t *have, const uint32_t *base, mi_cls_result_t *res_out,
+				     uint32_t *dec, uint32_t *idx, mi_cls_pool_out_t *out)
+{
+	const int rc = pool_check(c, res, len, n, tab, have, base, res_out, dec, idx, out);
+	if (rc)
+		return rc;
+	return host_run(c, nullptr,
+			[&] { return pool_host_launch(c, res, len, own, n, tab, have, base, res_out, dec, idx, out); });
+}
+
+extern "C" int mi_cls_pool_plan_host_submit(mi_cls_ctx_t *c, const mi_cls_result_t *res, const uint16_t *len,
+					    const uint8_t *own, uint32_t n, const mi_cls_pool_tab_t *tab,
+					    const uint32_t *have, const uint32_t *base, mi_cls_result_t *res_out,
+					    uint32_t *dec, uint32_t *idx, mi_cls_pool_out_t *out, uint64_t *ticket)
+{
+	if (!ticket)
+		return -EINVAL;
+	*ticket = 0;
+	const int rc = pool_check(c, res, len, n, tab, have, base, res_out, dec, idx, out);
+	if (rc)
+		return rc;
+	return host_run(c, ticket,
+			[&] { return pool_host_launch(c, res, len, own, n, tab, have, base, res_out, dec, idx, out); });
+}
+
+extern "C" int mi_cls_pool_plan_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
 {
 	return feature_host_wait(c, ticket);
 }

@@ -2978,6 +2978,29 @@ struct RunArgs {
 // n == 0: out alone.  preload: resolve the kernels only.
 int mi_cls_launch_run(hipStream_t st, const RunArgs &a, bool preload);
 
+// the pool plan (mi_cls_pool_plan; kernels: mi_cls_pool_dev.h, mi_cls_ka.hip)
+struct PoolArgs {
+	const mi_cls_result_t *res;
+	const uint16_t *len;
+	const uint8_t *own;            // NULL: no frame has a packet of its own
+	const mi_cls_pool_tab_t *tab;  // the device copy
+	uint32_t n;
+	uint32_t nslot;
+	uint32_t grid;                 // blocks of the count and place launches
+	uint32_t tpb;                  // tiles per block
+	uint32_t have[MI_CLS_POOL_SLOTS];
+	uint32_t base[MI_CLS_POOL_SLOTS];
+	uint32_t *cnt;                 // scratch: MI_CLS_POOL_SLOTS x grid ranked records, slot-major
+	unsigned long long *ctr;       // scratch: the INPLACE and TOO_LONG records, zeroed before the launches
+	mi_cls_result_t *res_out;
+	uint32_t *dec;
+	uint32_t *idx;
+	mi_cls_pool_out_t *out;
+};
+// The pool plan's launches on `st`, in order: count, place, finish; n == 0:
+// finish alone.  preload: resolve the kernels only.
+int mi_cls_launch_pool(hipStream_t st, const PoolArgs &a, bool preload);
+
 // Every launcher goes through mi_launch.  grid == 0 launches nothing: it
 // resolves the instantiation on the current device (hipFuncGetAttributes
 // loads the code object that holds it), so mi_cls_ctx_create can load every

@@ -1,6 +1,7 @@
 // mi_cls_rank_dev.h -- the wave step of a stable rank, shared by the receive
-// chain's decide kernel (mi_cls_kd.hip) and the enqueue plan's kernels
-// (mi_cls_enq_dev.h): a lane's rank among the lanes of its value is
+// chain's decide kernel (mi_cls_kd.hip), the enqueue plan's kernels
+// (mi_cls_enq_dev.h) and the pool plan's (mi_cls_pool_dev.h): a lane's rank
+// among the lanes of its value is
 // popcount(match_lanes(v) & lanes below); the counts of the waves before it
 // are the caller's.
 #ifndef MI_CLS_RANK_DEV_H_

@@ -1601,6 +1601,103 @@ int odp_amd_cls_enq_runs_host_wait(odp_pktio_t h, uint64_t ticket)
 	return ticket && e->ctx ? mi_cls_enq_runs_host_wait(e->ctx, ticket) : ticket ? -EINVAL : 0;
 }
 
+/* The control plane's part of the pool plan's table (mi_cls_pool_tab_t,
+ * mi_cls.h) for a pktio whose own pool is pktio_pool: slot 0 is that pool; each
+ * valid CoS whose action is ENQUEUE maps to the slot of its own pool, or to
+ * slot 0 without one (_odp_cls_classify_packet :1760-1764); further slots are
+ * numbered in order of first appearance scanning CoS index.  DROP and invalid
+ * CoS have no slot (0xFF).  pools[] (room for MI_CLS_POOL_SLOTS): each slot's
+ * pool; slot_cap is the caller's (odp_amd_cls_pooltab_fill, which knows the
+ * runtime's pools).  -E2BIG past MI_CLS_POOL_SLOTS pools. */
+int odp_amd_cls_pooltab_cos(odp_pool_t pktio_pool, struct mi_cls_pool_tab *tab, odp_pool_t pools[],
+			    uint32_t *nslot, uint64_t *gen)
+{
+	static uint64_t stamps;   /* under G.lock */
+	uint32_t ns = 1;
+	int rc = 0;
+
+	if (!tab || !pools || !nslot || !gen)
+		return -EINVAL;
+	memset(tab, 0, sizeof(*tab));
+	memset(tab->cos_slot, 0xFF, sizeof(tab->cos_slot));
+	pools[0] = pktio_pool;
+	pthread_mutex_lock(&G.lock);
+	*gen = G.gen;
+	for (uint32_t i = 0; G.init && i < G.max_cos && i < 256; i++) {
+		const cos_t *c = &G.cos[i];
+
+		if (!c->valid || c->action != ODP_COS_ACTION_ENQUEUE)
+			continue;
+		const odp_pool_t pool = c->pool != ODP_POOL_INVALID ? c->pool : pktio_pool;
+		uint32_t k = 0;
+
+		while (k < ns && pools[k] != pool)
+			k++;
+		if (k == ns) {
+			if (ns == MI_CLS_POOL_SLOTS) {
+				rc = -E2BIG;
+				break;
+			}
+			pools[ns++] = pool;
+		}
+		tab->cos_slot[i] = (uint8_t)k;
+	}
+	tab->stamp = ++stamps;
+	pthread_mutex_unlock(&G.lock);
+	tab->nslot = ns;
+	*nslot = ns;
+	return rc;
+}
+
+int odp_amd_cls_pool_plan(odp_pktio_t h, const void *res_dev, const uint16_t *len_dev, const uint8_t *own_dev,
+			  uint32_t n, const struct mi_cls_pool_tab *tab, const uint32_t have[],
+			  const uint32_t base[], void *res_out_dev, uint32_t *dec_dev, uint32_t *idx_dev,
+			  struct mi_cls_pool_out *out_dev, void *stream)
+{
+	mi_cls_ctx_t *c;
+	const int rc = enq_ctx(h, &c);
+
+	return rc ? rc : mi_cls_pool_plan(c, (const mi_cls_result_t *)res_dev, len_dev, own_dev, n, tab, have, base,
+					  (mi_cls_result_t *)res_out_dev, dec_dev, idx_dev, out_dev, stream);
+}
+
+int odp_amd_cls_pool_plan_host(odp_pktio_t h, const void *res, const uint16_t *len, const uint8_t *own,
+			       uint32_t n, const struct mi_cls_pool_tab *tab, const uint32_t have[],
+			       const uint32_t base[], void *res_out, uint32_t *dec, uint32_t *idx,
+			       struct mi_cls_pool_out *out)
+{
+	mi_cls_ctx_t *c;
+	const int rc = enq_ctx(h, &c);
+
+	return rc ? rc : mi_cls_pool_plan_host(c, (const mi_cls_result_t *)res, len, own, n, tab, have, base,
+					       (mi_cls_result_t *)res_out, dec, idx, out);
+}
+
+int odp_amd_cls_pool_plan_host_submit(odp_pktio_t h, const void *res, const uint16_t *len, const uint8_t *own,
+				      uint32_t n, const struct mi_cls_pool_tab *tab, const uint32_t have[],
+				      const uint32_t base[], void *res_out, uint32_t *dec, uint32_t *idx,
+				      struct mi_cls_pool_out *out, uint64_t *ticket)
+{
+	mi_cls_ctx_t *c;
+	int rc;
+
+	if (!ticket)
+		return -EINVAL;
+	*ticket = 0;
+	rc = enq_ctx(h, &c);
+	return rc ? rc : mi_cls_pool_plan_host_submit(c, (const mi_cls_result_t *)res, len, own, n, tab, have,
+						      base, (mi_cls_result_t *)res_out, dec, idx, out, ticket);
+}
+
+int odp_amd_cls_pool_plan_host_wait(odp_pktio_t h, uint64_t ticket)
+{
+	pktio_t *e = get_pktio(h);
+
+	if (!e)
+		return -EINVAL;
+	return ticket && e->ctx ? mi_cls_pool_plan_host_wait(e->ctx, ticket) : ticket ? -EINVAL : 0;
+}
+
 /* One burst's receive chain (mi_cls_rx_chain_submit) on the pktio's
  * context, under the current rules.  -ENOTSUP for pktios over several
  * devices (they take the host-decided delivery). */

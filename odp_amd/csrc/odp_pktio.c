@@ -280,6 +280,45 @@ odp_pktio_t odp_pktio_open(const char *name, odp_pool_t pool, const odp_pktio_pa
 	return h;
 }
 
+/* The pool plan's table for this pktio: the control plane's slots
+ * (odp_amd_cls_pooltab_cos, under its lock) over the pktio's pool, then each
+ * slot's packet capacity from the runtime's pools, the value the receive
+ * table's pool_cap takes.  Host only. */
+int odp_amd_cls_pooltab_fill(odp_pktio_t h, struct mi_cls_pool_tab *tab, odp_pool_t pools[], uint32_t *nslot,
+			     uint64_t *gen)
+{
+	rt_pktio_t *e = get_pk(h);
+
+	if (!e || !tab || !pools || !nslot || !gen)
+		return -EINVAL;
+	const int rc = odp_amd_cls_pooltab_cos(e->pool, tab, pools, nslot, gen);
+
+	for (uint32_t k = 0; rc == 0 && k < *nslot && k < MI_CLS_POOL_SLOTS; k++) {
+		const rt_pool_t *rp = rt_pool(pools[k]);
+
+		if (!rp || rp->param.type != ODP_POOL_PACKET)
+			return -EINVAL;
+		tab->slot_cap[k] = rp->data_cap;
+	}
+	return rc;
+}
+
+int odp_amd_cls_pool_own(const odp_packet_t pk[], uint32_t n, const odp_pool_t pools[], uint32_t nslot,
+			 uint8_t own[])
+{
+	if ((n && (!pk || !own)) || (nslot && !pools) || nslot > MI_CLS_POOL_SLOTS)
+		return -EINVAL;
+	for (uint32_t i = 0; i < n; i++) {
+		const odp_pool_t p = pk[i] != ODP_PACKET_INVALID ? odp_packet_pool(pk[i]) : ODP_POOL_INVALID;
+		uint32_t k = 0;
+
+		while (k < nslot && pools[k] != p)
+			k++;
+		own[i] = (uint8_t)(k < nslot ? k + 1u : 0u);
+	}
+	return 0;
+}
+
 odp_pktio_t odp_pktio_lookup(const char *name)
 {
 	for (int i = 0; i < RT_MAX_PKTIO; i++)
