@@ -1115,6 +1115,114 @@ int mi_cls_pool_plan_host_submit(mi_cls_ctx_t *ctx, const mi_cls_result_t *res_h
 				 uint64_t *ticket);
 int mi_cls_pool_plan_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
 
+/* ------------------------------------------------------------------------
+ * The pool move: the steps of the reference's receive loop that touch packet
+ * memory, for a batch the pool plan has decided: packet_parse_reset plus the
+ * parse and classification result written into the header (pktio/loop.c:
+ * 308-342) and the copy half of _odp_pktio_packet_to_pool (include/
+ * odp_packet_io_internal.h:352-371).  With it the chain classify -> pool plan
+ * -> pool move -> enqueue plan (or run plan) runs on one stream and the host
+ * reads back ent[] and the counters.  The classifier is on, so the parser
+ * layer is ALL: no layer cut.  Per record i, fate = dec[i] & 15:
+ *   FRESH    the packet is got[idx[i]] (the address of its mi_cls_pkt_meta_t
+ *            line).  All 64 bytes of the line are written: data_off =
+ *            headroom, len, in_flags, err, cos, cls_mark, l2 = 0, l3, l4,
+ *            input, every reserved word 0; dst_queue = dst_queue[id] when tab
+ *            maps the record's (cos, queue) by the enqueue plan's "delivered"
+ *            rule (outcome MI_CLS_OUT_ENQ, queue < cos_nq[cos], cos_q0[cos] +
+ *            queue < MI_CLS_ENQ_ENT, the entry's id < ndst), else 0; user_ptr
+ *            = that of pk[i]'s line when pk is given and pk[i] != 0 (what
+ *            odp_packet_copy carries), else 0.  The frame pkts[off[i] ..
+ *            off[i] + len[i]) is copied to line + data_from_meta in 16-byte
+ *            pieces: [0, len) is the frame, [len, round_up(len, 16)) is
+ *            unspecified, nothing at or past that is touched; len 0 writes
+ *            the line alone;
+ *   INPLACE  the packet is pk[i].  The line is written the same way, but
+ *            data_off and user_ptr keep the values read from it; no frame
+ *            byte is written;
+ *   other    ent[i] = 0, nothing else written.
+ * ent[i] is the line's address of the packet that holds frame i afterwards,
+ * or 0.  out: moved (FRESH records done), inplace (INPLACE records done),
+ * bytes (the sum of len over the moved records) and refused.
+ * Guards: no caller data can make the device touch memory outside pkts[0 ..
+ * pkts_bytes) and [arena_lo, arena_lo + arena_bytes), the one range every
+ * packet lies in.  A FRESH or INPLACE record is refused -- ent[i] = 0, nothing
+ * of it written, counted in refused -- when
+ *   its frame reaches past pkts_bytes (a frame needs [off, off + len) alone:
+ *   no slack behind it);
+ *   FRESH: idx[i] >= ngot; its packet's address is 0 or not 64-byte aligned;
+ *   [line, line + data_from_meta + round_up(len, 16)) is not inside the arena;
+ *   or pk[i] != 0 is not the address of a 64-byte line inside the arena;
+ *   INPLACE: pk is NULL; pk[i] is 0 or not 64-byte aligned; [line, line + 64)
+ *   is not inside the arena.
+ * Two records that name one packet, a packet that overlaps pkts where a FRESH
+ * record reads it, and arrays that overlap the arena's packets are undefined
+ * behaviour (inside the two ranges).
+ * Multi-GPU: there is no mi_cls_group_* form.
+ * ---------------------------------------------------------------------- */
+/* The kernel's shape: a wave takes tiles of MI_CLS_MOVE_TILE records (one per
+ * lane), dealt statically over at most MI_CLS_MOVE_GRID blocks (of 4 waves:
+ * wave w of W takes tiles w, w + W, ...); a tile's frames are copied in rounds
+ * of at most MI_CLS_MOVE_ROUND bytes, whose loads are all issued before the
+ * first store. */
+#define MI_CLS_MOVE_TILE 64
+#define MI_CLS_MOVE_GRID 512
+#define MI_CLS_MOVE_ROUND 8192
+
+typedef struct mi_cls_move_out {
+	uint64_t moved, inplace, bytes, refused;
+} mi_cls_move_out_t;
+
+typedef struct mi_cls_move_args {
+	const uint8_t *pkts;           /* the classification's frames ...               */
+	uint64_t pkts_bytes;           /* ... their buffer's size, < 2^32 ...           */
+	const uint32_t *off;           /* ... and arrays, at any alignment              */
+	const uint16_t *len;
+	const mi_cls_result_t *res;    /* the pool plan's res_out (16-byte aligned)     */
+	const uint32_t *dec, *idx;     /* the pool plan's outputs                       */
+	const uint64_t *got;           /* ngot line addresses of the packets taken, as
+					* the pool plan's base / have lay them out      */
+	const uint64_t *pk;            /* each frame's own packet's line, 0: none; NULL:
+					* no frame has one (pcap-style frames)          */
+	uint32_t n, ngot;
+	const mi_cls_enq_tab_t *tab;   /* host memory, read during the call             */
+	const uint64_t *dst_queue;     /* tab->ndst odp_queue_t by destination id; host
+					* memory; part of the table: refreshed with it  */
+	uint64_t input;                /* odp_pktio_t                                   */
+	uint32_t headroom;             /* data_off of a fresh packet                    */
+	uint32_t data_from_meta;       /* bytes from a line to a fresh packet's data: a
+					* multiple of 16, at least 64                   */
+	uint64_t arena_lo, arena_bytes;
+	uint64_t *ent;                 /* out: n line addresses                         */
+	mi_cls_move_out_t *out;        /* out (8-byte aligned)                          */
+} mi_cls_move_args_t;
+
+/* Move n records in device memory (or host memory the device addresses).  ent
+ * and out are written whole, no input value of theirs is read.  args, tab and
+ * dst_queue are host memory, read during the call; the table's device copy is
+ * refreshed when tab's address or stamp differs from the last call's.  The
+ * context needs no rules.  Stream-ordered on `stream`; returns after the
+ * launches are enqueued; a call on another stream than the previous move's is
+ * ordered after it.  n == 0: out is zeroed (the arrays may be NULL).
+ * -EINVAL: NULL args, table, dst_queue (with ndst > 0), out or (n > 0) array
+ * other than pk; got NULL with ngot > 0; a misaligned res (16), ent, got, pk or
+ * out (8); data_from_meta below 64 or no multiple of 16; n > MI_CLS_MAX_BATCH;
+ * pkts_bytes >= 2^32; arena_lo + arena_bytes past 2^64; a NULL context where
+ * there is a device.  -E2BIG: tab->ndst > MI_CLS_ENQ_DST_MAX.  -ENODEV: no
+ * device.  mi_cls_last_launch: info[0] 320 + the waves per block (324), [1]
+ * the launches (2; 1 for n == 0), [2]-[5] 0, [6] the grid. */
+int mi_cls_pool_move(mi_cls_ctx_t *ctx, const mi_cls_move_args_t *args, void *stream);
+
+/* Host-memory batch, as mi_cls_pool_plan_host and its submit / wait forms.
+ * The packets are always worked on in place: -EINVAL unless
+ * mi_cls_host_mapped holds for both ends of the arena.  pkts, off, len, res,
+ * dec, idx, got, pk (if given), ent and out all page-locked: read and written
+ * in place; otherwise the frames, off, len, res, dec, idx, got and pk go
+ * through the context's staging buffers and ent and out are copied back. */
+int mi_cls_pool_move_host(mi_cls_ctx_t *ctx, const mi_cls_move_args_t *args);
+int mi_cls_pool_move_host_submit(mi_cls_ctx_t *ctx, const mi_cls_move_args_t *args, uint64_t *ticket);
+int mi_cls_pool_move_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
+
 /* 1 if p lies in page-locked host memory that the device addresses at the
  * same address (the receive delivery's requirement), else 0. */
 int mi_cls_host_mapped(const void *p);

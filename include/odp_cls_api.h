@@ -505,6 +505,26 @@ int odp_amd_cls_pool_plan_host_submit(odp_pktio_t pktio, const void *res, const 
 				      uint64_t *ticket);
 int odp_amd_cls_pool_plan_host_wait(odp_pktio_t pktio, uint64_t ticket);
 
+/* The pool move of a planned batch on the pktio's context (mi_cls_pool_move
+ * and its host forms, mi_cls.h): every FRESH record's frame copied into the
+ * packet the pool plan gave it, the metadata lines of the FRESH and INPLACE
+ * records written, ent[] the packets that hold the frames afterwards.
+ * -ENOTSUP on pktios over several GPUs, as the pool plan. */
+struct mi_cls_move_args;
+int odp_amd_cls_pool_move(odp_pktio_t pktio, const struct mi_cls_move_args *args, void *stream);
+int odp_amd_cls_pool_move_host(odp_pktio_t pktio, const struct mi_cls_move_args *args);
+int odp_amd_cls_pool_move_host_submit(odp_pktio_t pktio, const struct mi_cls_move_args *args, uint64_t *ticket);
+int odp_amd_cls_pool_move_host_wait(odp_pktio_t pktio, uint64_t ticket);
+
+/* What the pool move needs to know of the runtime's packets: a packet's
+ * metadata line (mi_cls_pkt_meta_t: got[] / pk[] / ent[] hold its address) lies
+ * *meta_off bytes behind the packet handle, a fresh packet's data
+ * *data_from_meta behind the line, and every packet of a page-locked pool
+ * inside [*arena_lo, *arena_lo + *arena_bytes).  0; -EINVAL (a NULL argument);
+ * -ENOENT when no pool is page-locked (the layout is still written). */
+int odp_amd_cls_pool_move_geom(uint32_t *meta_off, uint32_t *data_from_meta, uint64_t *arena_lo,
+			       uint64_t *arena_bytes);
+
 /* Device contexts of the pktio (its GPUs, ODP_AMD_GPUS / create_multi); 1
  * for a single-device pktio, < 0 on error. */
 int odp_amd_cls_devices(odp_pktio_t pktio);

@@ -80,12 +80,13 @@ def build(force: bool = False, out_dir: str = PKG, defines=(), src_dir: str = SR
     host_deps = [asm_src, spec_src, prog_hdr, os.path.join(SRC, "mi_cls_asm.h"),
                  os.path.join(SRC, "mi_cls_spec.h")]
     k_srcs = [os.path.join(SRC, f"mi_cls_k{w}.hip") for w in (4, 8, 12, 16, "f", "f12", "f16", "c4",
-                                                              "c16", "d", "t", "h", "p", "l", "q", "r", "a")]
+                                                              "c16", "d", "t", "h", "p", "l", "q", "r", "a", "m")]
     tx_hdr = os.path.join(SRC, "mi_cls_tx_dev.h")
     parse_hdr = os.path.join(SRC, "mi_cls_parse_dev.h")
     lso_hdr = os.path.join(SRC, "mi_cls_lso_dev.h")
     enq_hdrs = [os.path.join(SRC, "mi_cls_enq_dev.h"), os.path.join(SRC, "mi_cls_rank_dev.h"),
-                os.path.join(SRC, "mi_cls_run_dev.h"), os.path.join(SRC, "mi_cls_pool_dev.h")]
+                os.path.join(SRC, "mi_cls_run_dev.h"), os.path.join(SRC, "mi_cls_pool_dev.h"),
+                os.path.join(SRC, "mi_cls_move_dev.h")]
     variant = bool(defines) or src_dir != globals()["SRC"]
     if force or variant or _stale(mi_so, [mi_src, mi_hdr, tx_hdr, parse_hdr, lso_hdr] + enq_hdrs + host_deps + k_srcs + hdrs + [__file__]):
         # one translation unit per block shape + the host code, compiled in

@@ -237,6 +237,71 @@ def _pool_u32x16(v):
     return a
 
 
+# the pool move (include/mi_cls.h): the kernel's shape (a wave's tile of
+# records, the blocks' bound, the bytes of a copy round)
+MOVE_TILE, MOVE_GRID, MOVE_ROUND = 64, 512, 8192
+
+
+class MoveOut(C.Structure):
+    """mi_cls_move_out_t."""
+    _fields_ = [("moved", C.c_uint64), ("inplace", C.c_uint64), ("bytes", C.c_uint64), ("refused", C.c_uint64)]
+
+
+MOVE_OUT_FIELDS = tuple(f[0] for f in MoveOut._fields_)
+
+
+class MoveArgs(C.Structure):
+    """mi_cls_move_args_t."""
+    _fields_ = [("pkts", C.c_void_p), ("pkts_bytes", C.c_uint64), ("off", C.c_void_p), ("len", C.c_void_p),
+                ("res", C.c_void_p), ("dec", C.c_void_p), ("idx", C.c_void_p), ("got", C.c_void_p),
+                ("pk", C.c_void_p), ("n", C.c_uint32), ("ngot", C.c_uint32), ("tab", C.POINTER(EnqTab)),
+                ("dst_queue", C.c_void_p), ("input", C.c_uint64), ("headroom", C.c_uint32),
+                ("data_from_meta", C.c_uint32), ("arena_lo", C.c_uint64), ("arena_bytes", C.c_uint64),
+                ("ent", C.c_void_p), ("out", C.c_void_p)]
+
+
+def move_args(tab, dst_queue, **kw) -> MoveArgs:
+    """A mi_cls_move_args_t: tab an EnqTab (None: NULL), dst_queue the
+    odp_queue_t of each destination id (a sequence; None: NULL), every other
+    field by keyword -- pointers as ints (0 / None: NULL).  The table and the
+    queue array stay alive with the returned struct."""
+    a = MoveArgs()
+    if tab is not None:
+        a.tab = C.pointer(tab)
+    if dst_queue is not None:
+        q = np.ascontiguousarray(dst_queue, dtype=np.uint64)
+        q = q if q.shape[0] else np.zeros(1, np.uint64)
+        a.dst_queue = q.ctypes.data
+        a._dst_queue = q
+    a._tab = tab
+    for k, v in kw.items():
+        if k not in dict(MoveArgs._fields_) or k in ("tab", "dst_queue"):
+            raise TypeError(f"move_args: no field {k}")
+        setattr(a, k, v or None if dict(MoveArgs._fields_)[k] is C.c_void_p else int(v))
+    return a
+
+
+def move_out_dict(words):
+    """The four uint64 of a mi_cls_move_out_t as a dict."""
+    return {k: int(v) for k, v in zip(MOVE_OUT_FIELDS, words)}
+
+
+def _move_host(L, prefix, handle, args, submit):
+    """The host forms of `prefix` (mi_cls_pool_move_host /
+    odp_amd_cls_pool_move_host).  submit: the _submit / _wait pair; "ticket":
+    the _submit alone, returning the ticket.  Returns the C status otherwise."""
+    if submit:
+        t = C.c_uint64()
+        rc = getattr(L, prefix + "_submit")(handle, C.byref(args), C.byref(t))
+        if rc == 0 and submit == "ticket":
+            return t.value
+        if rc == 0:
+            rc = getattr(L, prefix + "_wait")(handle, t.value)
+    else:
+        rc = getattr(L, prefix)(handle, C.byref(args))
+    return rc
+
+
 def run_out_dict(words):
     """The 24 uint64 of a mi_cls_run_out_t as a dict (vec_need: a list)."""
     w = [int(v) for v in words]
@@ -369,6 +434,16 @@ def _load():
         "odp_amd_cls_pool_plan_host_submit": (i32, [vp, vp, vp, vp, u32, C.POINTER(PoolTab), vp, vp, vp, vp, vp,
                                                     vp, C.POINTER(C.c_uint64)]),
         "odp_amd_cls_pool_plan_host_wait": (i32, [vp, C.c_uint64]),
+        "mi_cls_pool_move": (i32, [vp, C.POINTER(MoveArgs), vp]),
+        "mi_cls_pool_move_host": (i32, [vp, C.POINTER(MoveArgs)]),
+        "mi_cls_pool_move_host_submit": (i32, [vp, C.POINTER(MoveArgs), C.POINTER(C.c_uint64)]),
+        "mi_cls_pool_move_host_wait": (i32, [vp, C.c_uint64]),
+        "odp_amd_cls_pool_move": (i32, [vp, C.POINTER(MoveArgs), vp]),
+        "odp_amd_cls_pool_move_host": (i32, [vp, C.POINTER(MoveArgs)]),
+        "odp_amd_cls_pool_move_host_submit": (i32, [vp, C.POINTER(MoveArgs), C.POINTER(C.c_uint64)]),
+        "odp_amd_cls_pool_move_host_wait": (i32, [vp, C.c_uint64]),
+        "odp_amd_cls_pool_move_geom": (i32, [C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_uint64)]),
         "odp_amd_cls_parse_host": (i32, [vp, C.c_size_t, vp, vp, u32, u32, u32, u32, vp]),
         "odp_amd_cls_parse_term": (None, []),
     }
@@ -852,6 +927,31 @@ class EnqContext(_FeatureContext):
         if rc != 0:
             raise RuntimeError(f"mi_cls_pool_plan_host_wait: {rc}")
 
+    def move_device(self, args, stream=0):
+        """mi_cls_pool_move on a MoveArgs of device pointers, stream-ordered.
+        Returns the C status."""
+        return self.L.mi_cls_pool_move(self.ctx, C.byref(args), stream or None)
+
+    def move(self, args):
+        """mi_cls_pool_move on torch's current stream, waited for."""
+        import torch
+        dev = torch.device(f"cuda:{self.gpu}")
+        rc = self.move_device(args, torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_pool_move: {rc} ({lib().mi_cls_strerror(rc).decode()})")
+        torch.cuda.synchronize(dev)
+
+    def move_host(self, args, submit=False):
+        """mi_cls_pool_move_host on a MoveArgs of host pointers (submit: the
+        _host_submit / _host_wait pair; "ticket": _host_submit alone, returns
+        the ticket for move_wait).  Returns the C status."""
+        return _move_host(self.L, "mi_cls_pool_move_host", self.ctx, args, submit)
+
+    def move_wait(self, ticket):
+        rc = self.L.mi_cls_pool_move_host_wait(self.ctx, ticket)
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_pool_move_host_wait: {rc}")
+
     def plan_device(self, d_res, d_len, n, tab, d_perm, d_gbeg, d_out, stream=0):
         """On device pointers (ints), stream-ordered.  Returns the C status."""
         return self.L.mi_cls_enq_plan(self.ctx, d_res or None, d_len or None, n, C.byref(tab),
@@ -1240,6 +1340,25 @@ class Classifier:
         _wait pair), as EnqContext.pools_host."""
         return _pool_plan_host(self.L, "odp_amd_cls_pool_plan_host", self.pktio, res, ln, own, tab, have, base,
                                res_out, dec, idx, out, submit)
+
+    def pool_move_geom(self):
+        """odp_amd_cls_pool_move_geom: (rc, meta_off, data_from_meta, arena_lo,
+        arena_bytes); rc -ENOENT when no pool is page-locked."""
+        mo, dfm = C.c_uint32(), C.c_uint32()
+        lo, nb = C.c_uint64(), C.c_uint64()
+        rc = self.L.odp_amd_cls_pool_move_geom(C.byref(mo), C.byref(dfm), C.byref(lo), C.byref(nb))
+        return rc, mo.value, dfm.value, lo.value, nb.value
+
+    def pool_move(self, args, stream=0):
+        """The pool move of a planned batch (odp_amd_cls_pool_move, on the
+        pktio's context) on a MoveArgs of device pointers, stream-ordered.
+        Returns the C status."""
+        return self.L.odp_amd_cls_pool_move(self.pktio, C.byref(args), stream or None)
+
+    def pool_move_host(self, args, submit=False):
+        """odp_amd_cls_pool_move_host (submit: the _submit / _wait pair), as
+        EnqContext.move_host."""
+        return _move_host(self.L, "odp_amd_cls_pool_move_host", self.pktio, args, submit)
 
     def cos_stats_packets(self, cos_handle):
         s = CosStats()

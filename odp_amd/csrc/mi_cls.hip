@@ -90,6 +90,18 @@ struct mi_cls_ctx {
 	hipEvent_t pool_ev = nullptr;
 	hipStream_t pool_last = nullptr;
 	bool pool_used = false;
+	// the pool move (mi_cls_pool_move), likewise: the scratch of fixed size (the
+	// table and dst_queue, the counters, the staged form's out), the staged
+	// form's dec, idx, got, pk and ent (move_st_cap entries), the table's
+	// snapshot and whose copy the device holds
+	uint8_t *d_move_fix = nullptr, *d_move_st = nullptr;
+	size_t move_st_cap = 0;
+	uint8_t *h_move_tab = nullptr;
+	const void *move_tab_src = nullptr;
+	uint64_t move_tab_stamp = 0;
+	hipEvent_t move_ev = nullptr;
+	hipStream_t move_last = nullptr;
+	bool move_used = false;
 	// program-specialised flat kernel for the loaded program (null: none)
 	std::shared_ptr<SpecCode> spec;
 	uint32_t batch_hint = 0; // largest batch per call (mi_cls_batch_hint), 0: unknown
@@ -180,6 +192,7 @@ static int preload_kernels(int device)
 	chk(mi_cls_launch_enq(nullptr, EnqArgs{}, 0, true));
 	chk(mi_cls_launch_run(nullptr, RunArgs{}, true));
 	chk(mi_cls_launch_pool(nullptr, PoolArgs{}, true));
+	chk(mi_cls_launch_move(nullptr, MoveArgs{}, true));
 	if (bad)
 		return bad;
 	done.insert(device);
@@ -290,6 +303,14 @@ extern "C" int mi_cls_ctx_destroy(mi_cls_ctx_t *c)
 	(void)hipFree(c->d_pool_st);
 	if (c->h_pool_tab)
 		(void)hipHostFree(c->h_pool_tab);
+	if (c->move_ev) {
+		(void)hipEventSynchronize(c->move_ev);
+		(void)hipEventDestroy(c->move_ev);
+	}
+	(void)hipFree(c->d_move_fix);
+	(void)hipFree(c->d_move_st);
+	if (c->h_move_tab)
+		(void)hipHostFree(c->h_move_tab);
 	(void)hipFree(c->d_rx);
 	if (c->h_tab)
 		(void)hipHostFree(c->h_tab);
@@ -2070,6 +2091,245 @@ extern "C" int mi_cls_pool_plan_host_submit(mi_cls_ctx_t *c, const mi_cls_result
 }
 
 extern "C" int mi_cls_pool_plan_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
+{
+	return feature_host_wait(c, ticket);
+}
+
+// -------------------------------------------------------------- the pool move
+// The pool move's scratch in the context, by the pool plan's policy.  Of fixed
+// size: the table's device copy with dst_queue behind it, the four counters
+// and the staged form's out.  The device path needs nothing per entry; the
+// staged host form keeps dec, idx (4 B each), pk and ent (8 B each) per record
+// and got (8 B per packet) in a buffer of its own, of move_st_cap entries each.
+#define MOVE_FIX_TAB 0u
+#define MOVE_FIX_DSTQ (MOVE_FIX_TAB + ENQ_ALIGN(sizeof(mi_cls_enq_tab_t)))
+#define MOVE_FIX_CTR (MOVE_FIX_DSTQ + ENQ_ALIGN((size_t)MI_CLS_ENQ_DST_MAX * 8u))
+#define MOVE_FIX_OUT (MOVE_FIX_CTR + ENQ_ALIGN(sizeof(mi_cls_move_out_t)))
+#define MOVE_FIX_BYTES (MOVE_FIX_OUT + ENQ_ALIGN(sizeof(mi_cls_move_out_t)))
+
+static uint64_t *move_st_ent(const mi_cls_ctx_t *c) { return (uint64_t *)c->d_move_st; }
+static uint64_t *move_st_pk(const mi_cls_ctx_t *c) { return (uint64_t *)(c->d_move_st + ENQ_ALIGN(8u * c->move_st_cap)); }
+static uint64_t *move_st_got(const mi_cls_ctx_t *c) { return (uint64_t *)(c->d_move_st + 2u * ENQ_ALIGN(8u * c->move_st_cap)); }
+static uint32_t *move_st_dec(const mi_cls_ctx_t *c) { return (uint32_t *)(c->d_move_st + 3u * ENQ_ALIGN(8u * c->move_st_cap)); }
+static uint32_t *move_st_idx(const mi_cls_ctx_t *c) { return move_st_dec(c) + ENQ_ALIGN(4u * c->move_st_cap) / 4u; }
+
+// Before the scratch is replaced, and before the table's snapshot or device
+// copy is rewritten, the previous move has ended (move_ev).
+static int move_idle(mi_cls_ctx_t *c)
+{
+	if (c->move_used)
+		HIP_OK(hipEventSynchronize(c->move_ev));
+	return 0;
+}
+
+// staged: entries of the staged host form (0: the device path)
+static int move_scratch(mi_cls_ctx_t *c, uint32_t staged)
+{
+	if (!c->d_move_fix) {
+		if (!c->move_ev && hipEventCreateWithFlags(&c->move_ev, hipEventDisableTiming) != hipSuccess)
+			return -EIO;
+		if ((!c->h_move_tab &&
+		     hipHostMalloc((void **)&c->h_move_tab, MOVE_FIX_CTR, hipHostMallocDefault) != hipSuccess) ||
+		    hipMalloc((void **)&c->d_move_fix, MOVE_FIX_BYTES) != hipSuccess)
+			return -ENOMEM;
+	}
+	if (staged > c->move_st_cap) {
+		const int rc = move_idle(c);
+		if (rc)
+			return rc;
+		(void)hipFree(c->d_move_st);
+		c->d_move_st = nullptr;
+		c->move_st_cap = 0;
+		const size_t cap = staged < 4096u ? 4096u : (size_t)staged + staged / 2;
+		if (hipMalloc((void **)&c->d_move_st, 3u * ENQ_ALIGN(8u * cap) + 2u * ENQ_ALIGN(4u * cap)) != hipSuccess)
+			return -ENOMEM;
+		c->move_st_cap = cap;
+	}
+	return 0;
+}
+
+// The table and the scalars first (host memory, no device needed), then the
+// context, then the batch
+static int move_check(const mi_cls_ctx_t *c, const mi_cls_move_args_t *a)
+{
+	if (!a || !a->tab || a->n > MI_CLS_MAX_BATCH || a->pkts_bytes > 0xFFFFFFFFull || a->data_from_meta < 64u ||
+	    (a->data_from_meta & 15u) != 0 || a->arena_lo + a->arena_bytes < a->arena_lo)
+		return -EINVAL;
+	if (a->tab->ndst > MI_CLS_ENQ_DST_MAX)
+		return -E2BIG;
+	if ((a->tab->ndst && !a->dst_queue) || (a->ngot && !a->got))
+		return -EINVAL;
+	if (!c)
+		return no_ctx();
+	if (!a->out || ((uintptr_t)a->out & 7u) != 0)
+		return -EINVAL;
+	if (a->n == 0)
+		return 0;
+	return a->pkts && a->off && a->len && a->res && a->dec && a->idx && a->ent && ((uintptr_t)a->res & 15u) == 0 &&
+			       (((uintptr_t)a->ent | (uintptr_t)a->got | (uintptr_t)a->pk) & 7u) == 0 ? 0 : -EINVAL;
+}
+
+extern "C" int mi_cls_pool_move(mi_cls_ctx_t *c, const mi_cls_move_args_t *h, void *stream)
+{
+	int rc = move_check(c, h);
+	if (rc)
+		return rc;
+	hipStream_t st = (hipStream_t)stream;
+	HIP_OK(set_device(c->device));
+	rc = move_scratch(c, 0);
+	if (rc)
+		return rc;
+	// the scratch is one move's at a time: a move on another stream follows
+	// the previous one
+	if (c->move_used && c->move_last != st)
+		HIP_OK(hipStreamWaitEvent(st, c->move_ev, 0));
+	// the table's device copy and dst_queue behind it, refreshed when the host
+	// table's stamp moved
+	const mi_cls_enq_tab_t *tab = h->tab;
+	const uint32_t ndst = tab->ndst;
+	if (!c->move_tab_src || c->move_tab_src != tab || c->move_tab_stamp != tab->stamp) {
+		rc = move_idle(c);
+		if (rc)
+			return rc;
+		memcpy(c->h_move_tab + MOVE_FIX_TAB, tab, sizeof(*tab));
+		if (ndst)
+			memcpy(c->h_move_tab + MOVE_FIX_DSTQ, h->dst_queue, (size_t)ndst * 8u);
+		c->move_tab_src = nullptr;
+		HIP_OK(hipMemcpyAsync(c->d_move_fix, c->h_move_tab, MOVE_FIX_DSTQ + (size_t)ndst * 8u,
+				      hipMemcpyHostToDevice, st));
+		c->move_tab_src = tab;
+		c->move_tab_stamp = ((const mi_cls_enq_tab_t *)c->h_move_tab)->stamp;
+	}
+	MoveArgs a;
+	memset(&a, 0, sizeof(a));
+	a.pkts = h->pkts;
+	a.pkts_bytes = h->pkts_bytes;
+	a.off = h->off;
+	a.len = h->len;
+	a.res = h->res;
+	a.dec = h->dec;
+	a.idx = h->idx;
+	a.pk = h->pk;
+	a.tab = (const mi_cls_enq_tab_t *)(c->d_move_fix + MOVE_FIX_TAB);
+	a.dstq = (const uint64_t *)(c->d_move_fix + MOVE_FIX_DSTQ);
+	// the kernel reads got[0] for every record that takes none: without
+	// packets, a word of the scratch that nobody uses
+	a.got = h->ngot ? h->got : a.dstq;
+	a.n = h->n;
+	a.ngot = h->ngot;
+	a.ndst = ndst;
+	const uint64_t blocks = (((uint64_t)h->n + MI_CLS_MOVE_TILE - 1u) / MI_CLS_MOVE_TILE + MOVE_WAVES - 1u) /
+				MOVE_WAVES;
+	a.grid = (uint32_t)(blocks < MI_CLS_MOVE_GRID ? blocks : MI_CLS_MOVE_GRID);
+	a.headroom = h->headroom;
+	a.data_from_meta = h->data_from_meta;
+	a.input = h->input;
+	a.arena_lo = h->arena_lo;
+	a.arena_bytes = h->arena_bytes;
+	a.ctr = (unsigned long long *)(c->d_move_fix + MOVE_FIX_CTR);
+	a.ent = h->ent;
+	a.out = h->out;
+	// this call's counters start from zero, whatever the last one left
+	HIP_OK(hipMemsetAsync(a.ctr, 0, sizeof(mi_cls_move_out_t), st));
+	uint32_t *last = c->last;
+	last[0] = 320u + MOVE_WAVES;
+	last[1] = h->n ? 2u : 1u;
+	last[2] = last[3] = last[4] = last[5] = 0;
+	last[6] = a.grid;
+	rc = mi_cls_launch_move(st, a, false);
+	if (rc)
+		return rc;
+	HIP_OK(hipEventRecord(c->move_ev, st));
+	c->move_used = true;
+	c->move_last = st;
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+// The host forms' own condition: the packets are worked on in place
+static int move_host_check(const mi_cls_ctx_t *c, const mi_cls_move_args_t *a)
+{
+	const int rc = move_check(c, a);
+	if (rc)
+		return rc;
+	if (a->n == 0)
+		return 0;
+	return a->arena_bytes && mi_cls_host_mapped((const void *)(uintptr_t)a->arena_lo) &&
+			       mi_cls_host_mapped((const void *)(uintptr_t)(a->arena_lo + a->arena_bytes - 1u)) ? 0 : -EINVAL;
+}
+
+// A host batch on the context's stream, nothing waited for: in place when
+// every array is page-locked, else the frames, offsets and lengths through the
+// staging buffers (stage_up), the records through d_out, dec, idx, got, pk and
+// ent through the move's staging buffer and out through the scratch.
+static int move_host_launch(mi_cls_ctx_t *c, const mi_cls_move_args_t *h)
+{
+	HIP_OK(set_device(c->device));
+	mi_cls_move_args_t a = *h;
+	const uint32_t n = h->n, ngot = h->ngot;
+	if (dev_views(a.out) && (n == 0 || (dev_views(a.pkts, a.off, a.len, a.res, a.dec, a.idx, a.ent) &&
+					    (!ngot || dev_views(a.got)) && (!h->pk || dev_views(a.pk))))) {
+		if (n == 0)
+			a.pk = nullptr;
+		return mi_cls_pool_move(c, &a, c->stream);
+	}
+	a = *h;
+	int rc = move_scratch(c, n > ngot ? (n ? n : 1u) : ngot);
+	if (rc)
+		return rc;
+	mi_cls_move_out_t *dout = (mi_cls_move_out_t *)(c->d_move_fix + MOVE_FIX_OUT);
+	if (n) {
+		rc = stage_up(c, h->pkts, (size_t)h->pkts_bytes, (size_t)h->pkts_bytes, h->off, h->len, n, n);
+		if (rc)
+			return rc;
+		HIP_OK(hipMemcpyAsync(c->d_out, h->res, n * sizeof(mi_cls_result_t), hipMemcpyHostToDevice, c->stream));
+		HIP_OK(hipMemcpyAsync(move_st_dec(c), h->dec, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+		HIP_OK(hipMemcpyAsync(move_st_idx(c), h->idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+		if (ngot)
+			HIP_OK(hipMemcpyAsync(move_st_got(c), h->got, (size_t)ngot * 8u, hipMemcpyHostToDevice, c->stream));
+		if (h->pk)
+			HIP_OK(hipMemcpyAsync(move_st_pk(c), h->pk, (size_t)n * 8u, hipMemcpyHostToDevice, c->stream));
+		a.pkts = c->d_pk;
+		a.off = c->d_off;
+		a.len = c->d_len;
+		a.res = c->d_out;
+		a.dec = move_st_dec(c);
+		a.idx = move_st_idx(c);
+		a.got = ngot ? move_st_got(c) : nullptr;
+		a.pk = h->pk ? move_st_pk(c) : nullptr;
+		a.ent = move_st_ent(c);
+	}
+	a.out = dout;
+	rc = mi_cls_pool_move(c, &a, c->stream);
+	if (rc)
+		return rc;
+	if (n)
+		HIP_OK(hipMemcpyAsync(h->ent, move_st_ent(c), (size_t)n * 8u, hipMemcpyDeviceToHost, c->stream));
+	HIP_OK(hipMemcpyAsync(h->out, dout, sizeof(*dout), hipMemcpyDeviceToHost, c->stream));
+	// the scratch is this move's until the copies have read it
+	HIP_OK(hipEventRecord(c->move_ev, c->stream));
+	return 0;
+}
+
+extern "C" int mi_cls_pool_move_host(mi_cls_ctx_t *c, const mi_cls_move_args_t *a)
+{
+	const int rc = move_host_check(c, a);
+	if (rc)
+		return rc;
+	return host_run(c, nullptr, [&] { return move_host_launch(c, a); });
+}
+
+extern "C" int mi_cls_pool_move_host_submit(mi_cls_ctx_t *c, const mi_cls_move_args_t *a, uint64_t *ticket)
+{
+	if (!ticket)
+		return -EINVAL;
+	*ticket = 0;
+	const int rc = move_host_check(c, a);
+	if (rc)
+		return rc;
+	return host_run(c, ticket, [&] { return move_host_launch(c, a); });
+}
+
+extern "C" int mi_cls_pool_move_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
 {
 	return feature_host_wait(c, ticket);
 }

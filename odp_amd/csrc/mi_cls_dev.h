@@ -3001,6 +3001,36 @@ struct PoolArgs {
 // finish alone.  preload: resolve the kernels only.
 int mi_cls_launch_pool(hipStream_t st, const PoolArgs &a, bool preload);
 
+// the pool move (mi_cls_pool_move; kernels: mi_cls_move_dev.h, mi_cls_km.hip)
+#define MOVE_WAVES 4u                   // waves of a block
+struct MoveArgs {
+	const uint8_t *pkts;
+	uint64_t pkts_bytes;           // below 2^32: the source descriptor's size
+	const uint32_t *off;
+	const uint16_t *len;
+	const mi_cls_result_t *res;
+	const uint32_t *dec;
+	const uint32_t *idx;
+	const uint64_t *got;
+	const uint64_t *pk;            // NULL: no frame has a packet of its own
+	const mi_cls_enq_tab_t *tab;   // the device copy
+	const uint64_t *dstq;          // the device copy of dst_queue[ndst]
+	uint32_t n;
+	uint32_t ngot;
+	uint32_t ndst;
+	uint32_t grid;                 // blocks of the move launch
+	uint32_t headroom;
+	uint32_t data_from_meta;
+	uint64_t input;
+	uint64_t arena_lo, arena_bytes;
+	unsigned long long *ctr;       // scratch: the four counters, zeroed before the launches
+	uint64_t *ent;
+	mi_cls_move_out_t *out;
+};
+// The pool move's launches on `st`, in order: move, finish; n == 0: finish
+// alone.  preload: resolve the kernels only.
+int mi_cls_launch_move(hipStream_t st, const MoveArgs &a, bool preload);
+
 // Every launcher goes through mi_launch.  grid == 0 launches nothing: it
 // resolves the instantiation on the current device (hipFuncGetAttributes
 // loads the code object that holds it), so mi_cls_ctx_create can load every

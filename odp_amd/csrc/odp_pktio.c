@@ -319,6 +319,29 @@ int odp_amd_cls_pool_own(const odp_packet_t pk[], uint32_t n, const odp_pool_t p
 	return 0;
 }
 
+/* The pool move's geometry: the runtime's packet layout (a packet handle is
+ * its header's address; its metadata line lies meta_off behind it and a fresh
+ * packet's data data_from_meta behind the line) and the one range all
+ * page-locked pools lie in.  -ENOENT when there is none (pageable pools). */
+int odp_amd_cls_pool_move_geom(uint32_t *meta_off, uint32_t *data_from_meta, uint64_t *arena_lo,
+			       uint64_t *arena_bytes)
+{
+	uint8_t *lo;
+	size_t span;
+
+	if (!meta_off || !data_from_meta || !arena_lo || !arena_bytes)
+		return -EINVAL;
+	*meta_off = (uint32_t)__builtin_offsetof(pkt_hdr_t, meta);
+	*data_from_meta = rt_data_from_meta();
+	*arena_lo = 0;
+	*arena_bytes = 0;
+	if (!rt_pinned_arena(&lo, &span))
+		return -ENOENT;
+	*arena_lo = (uint64_t)(uintptr_t)lo;
+	*arena_bytes = span;
+	return 0;
+}
+
 odp_pktio_t odp_pktio_lookup(const char *name)
 {
 	for (int i = 0; i < RT_MAX_PKTIO; i++)
