@@ -1223,6 +1223,136 @@ int mi_cls_pool_move_host(mi_cls_ctx_t *ctx, const mi_cls_move_args_t *args);
 int mi_cls_pool_move_host_submit(mi_cls_ctx_t *ctx, const mi_cls_move_args_t *args, uint64_t *ticket);
 int mi_cls_pool_move_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
 
+/* ------------------------------------------------------------------------
+ * The vector fill: the host half of the reference's _odp_cos_vector_enq
+ * (include/odp_classification_internal.h:83-137) for a batch the run plan has
+ * cut: every run's event array, ready for one odp_queue_enq_multi, and the
+ * packet vectors of the runs that have some, filled.  With it the chain
+ * classify -> pool plan -> pool move -> run plan -> vector fill runs on one
+ * stream; nruns and the delivered count are read on the device from the run
+ * plan's out, so there is no host round trip between the plan and the fill.
+ * Inputs: the run plan's seq[n], runs[run_cap] and out, the pool move's ent[n],
+ * the vectors taken for the batch (vgot[nvgot], slot s's at vbase[s] ..
+ * vbase[s] + vhave[s]) and the run table.
+ *   handle       hnd(i) = ent[i] - ent_to_handle when ent[i] != 0, else 0
+ *                (ent_to_handle: the distance from a packet handle to its
+ *                metadata line).  A delivered record whose ent is 0 is one the
+ *                move refused: it is written as handle 0 wherever it lands,
+ *                and every handle 0 written to ev, a table or lost is counted
+ *                in holes.
+ * Per run r < nruns, in run order, with s = vslot[cos], vm = vmax[cos],
+ * rank_s(r) = the sum of nvec over the earlier MI_CLS_RUN_VEC runs of slot s,
+ * ev_first(r) = the sum over the earlier runs of (count for a plain run, nvec
+ * for a vector run): ev needs at most n entries and no entry's place depends
+ * on a pool running short:
+ *   plain run    (flags has no MI_CLS_RUN_VEC) its events are its packets:
+ *                ev[ev_first + o] = hnd(seq[first + o]) for o < count;
+ *                ev_count = pk_enq = count;
+ *   vector run   it gets g = clamp(vhave[s] - rank_s(r), 0, nvec) vectors,
+ *                vgot[vbase[s] + rank_s(r) + k] for k < g: the reference's
+ *                allocate-until-it-fails loop under "no vector returns to a
+ *                pool during the batch" (the pool plan's assumption): the run
+ *                at which a pool runs out gets what is left, later runs of the
+ *                pool none.  Vector k: size = min(vm, count - k * vm), tbl[j] =
+ *                hnd(seq[first + k * vm + j]); ev[ev_first + k] = the vector
+ *                (its vgot value) for k < g, 0 for g <= k < nvec; ev_count =
+ *                g; pk_enq = min(count, g * vm).  The packets seq[first +
+ *                pk_enq .. first + count) are lost: their handles are appended
+ *                to lost[] in no specified order (a free list; the reference
+ *                leaks them).  They reach no queue: queue discards.
+ * evr[r] = { ev_first, ev_count, pk_enq, vfirst }, vfirst the index in vgot of
+ * the run's first vector, 0xFFFFFFFF for a plain run or g == 0; written for
+ * r < nruns only.  ev is written in [0, ev_span) only, lost in [0, out->lost).
+ * out: events (ev_count summed), ev_span (the event places: ev_first + its
+ * share of the last run), vectors (filled), in_vectors (the packets in them),
+ * lost, holes, refused, truncated, vec_used[s] = min(the slot's nvec sum,
+ * vhave[s]): the vectors from vbase[s] + vec_used[s] on go back to the pool.
+ * out->nruns > run_cap of the run plan: the plan was truncated, and the fill
+ * writes nothing but its own out: truncated = 1, every other field 0.
+ * Guards: no caller data can make the device touch memory outside the arrays
+ * and [varena_lo, varena_lo + varena_bytes), the one range every vector lies
+ * in.  A vector is refused -- nothing of it written, its ev entry 0, counted
+ * in refused; its packets stay reachable through ent and are in no count --
+ * when its index is >= nvgot, its address is 0 or not 8-byte aligned, or [v, v
+ * + tbl_off + 8 * size) is not inside the arena.  seq values are checked
+ * against n before use, first + count is clamped to min(out->delivered, n),
+ * and an ev or lost place at or past n is not written.  ev, evr and lost must
+ * not alias the inputs; vectors that overlap each other or the arrays are
+ * undefined behaviour (inside the ranges).
+ * Multi-GPU: there is no mi_cls_group_* form.  A shard's ranks start at zero,
+ * so the caller gives each shard its own vhave / vbase (its part of the
+ * vectors).
+ * ---------------------------------------------------------------------- */
+/* The kernels' shape: a block of 16 waves walks a contiguous run of tiles of
+ * MI_CLS_VEC_TILE runs (count, place) or delivered places (fill); at most
+ * MI_CLS_VEC_GRID blocks (grid = min(MI_CLS_VEC_GRID, tiles)). */
+#define MI_CLS_VEC_TILE 1024
+#define MI_CLS_VEC_GRID 256
+
+typedef struct mi_cls_evrun {
+	uint32_t ev_first;             /* the run's first place in ev                   */
+	uint32_t ev_count;             /* events to enqueue from there                  */
+	uint32_t pk_enq;               /* packets they carry; count - pk_enq are lost   */
+	uint32_t vfirst;               /* index in vgot of its first vector, 0xFFFFFFFF */
+} mi_cls_evrun_t;
+
+typedef struct mi_cls_vec_out {
+	uint64_t events, ev_span, vectors, in_vectors, lost, holes, refused, truncated;
+	uint64_t vec_used[MI_CLS_RUN_VSLOTS];
+} mi_cls_vec_out_t;
+
+typedef struct mi_cls_vec_args {
+	const uint32_t *seq;           /* the run plan's seq[n] ...                     */
+	const mi_cls_run_t *runs;      /* ... runs[run_cap] (16-byte aligned) ...       */
+	const mi_cls_run_out_t *run_out; /* ... and out, read on the device             */
+	const uint64_t *ent;           /* the pool move's ent[n]                        */
+	const uint64_t *vgot;          /* nvgot vector handles (their addresses)        */
+	uint32_t n, run_cap, nvgot;
+	uint32_t size_off, tbl_off;    /* a vector's size word and table, from its handle */
+	uint32_t rsv;
+	uint64_t ent_to_handle;
+	const mi_cls_run_tab_t *rtab;  /* host memory, read during the call             */
+	uint32_t vbase[MI_CLS_RUN_VSLOTS], vhave[MI_CLS_RUN_VSLOTS];
+	uint32_t vcap[MI_CLS_RUN_VSLOTS];   /* each slot's pool's max_size              */
+	uint64_t varena_lo, varena_bytes;
+	uint64_t *ev;                  /* out: n entries                                */
+	mi_cls_evrun_t *evr;           /* out: run_cap entries (16-byte aligned)        */
+	uint64_t *lost;                /* out: n entries                                */
+	mi_cls_vec_out_t *out;         /* out (8-byte aligned)                          */
+} mi_cls_vec_args_t;
+
+/* Fill the vectors and event arrays of a planned batch in device memory (or
+ * host memory the device addresses).  ev[0 .. ev_span), evr[0 .. nruns),
+ * lost[0 .. out->lost) and out are written whole, no input value of theirs is
+ * read and nothing past those ends is touched.  args and rtab are host memory,
+ * read during the call; the run table's device copy is refreshed when rtab's
+ * address or stamp differs from the last call's, and the fixed scratch is the
+ * context's (16 B per run of run_cap more, grown by 1.5x and kept).  The
+ * context needs no rules.  Stream-ordered on `stream`; returns after the
+ * launches are enqueued; a call on another stream than the previous fill's is
+ * ordered after it by an event.  n == 0: out is zeroed (the arrays may be
+ * NULL).  -EINVAL: NULL args, table, out or (n > 0) array (runs and evr may be
+ * NULL when run_cap == 0, vgot when nvgot == 0); a misaligned runs or evr
+ * (16), ent, vgot, ev, lost or out (8); size_off no multiple of 4 or size_off
+ * + 4 > tbl_off; tbl_off no multiple of 8; a MI_CLS_RUN_VEC CoS whose vmax is
+ * 0 or exceeds vcap[vslot] or whose vslot is >= MI_CLS_RUN_VSLOTS; vbase[s] +
+ * vhave[s] past nvgot; varena_lo + varena_bytes past 2^64; n >
+ * MI_CLS_MAX_BATCH; a NULL context where there is a device.  -ENODEV: no
+ * device.  mi_cls_last_launch: info[0] 384 + the waves per block (400), [1]
+ * the launches (4; 1 for n == 0), [2]-[5] 0, [6] the grid of the fill launch. */
+int mi_cls_vec_fill(mi_cls_ctx_t *ctx, const mi_cls_vec_args_t *args, void *stream);
+
+/* Host-memory batch, as mi_cls_pool_move_host and its submit / wait forms.
+ * The vectors are always worked on in place: -EINVAL unless
+ * mi_cls_host_mapped holds for both ends of the vector arena (n > 0).  seq,
+ * runs, run_out, ent, vgot, ev, evr, lost and out all page-locked: read and
+ * written in place; otherwise seq, runs, run_out, ent and vgot are staged up
+ * and ev, evr, lost and out are copied back (ev, evr and lost go up first, so
+ * that the entries the fill leaves alone come back as they were). */
+int mi_cls_vec_fill_host(mi_cls_ctx_t *ctx, const mi_cls_vec_args_t *args);
+int mi_cls_vec_fill_host_submit(mi_cls_ctx_t *ctx, const mi_cls_vec_args_t *args, uint64_t *ticket);
+int mi_cls_vec_fill_host_wait(mi_cls_ctx_t *ctx, uint64_t ticket);
+
 /* 1 if p lies in page-locked host memory that the device addresses at the
  * same address (the receive delivery's requirement), else 0. */
 int mi_cls_host_mapped(const void *p);

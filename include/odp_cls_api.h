@@ -525,6 +525,66 @@ int odp_amd_cls_pool_move_host_wait(odp_pktio_t pktio, uint64_t ticket);
 int odp_amd_cls_pool_move_geom(uint32_t *meta_off, uint32_t *data_from_meta, uint64_t *arena_lo,
 			       uint64_t *arena_bytes);
 
+/* The vector fill of a planned batch on the pktio's context (mi_cls_vec_fill
+ * and its host forms, mi_cls.h): every run's event array and its packet
+ * vectors, ready for odp_amd_cls_vec_enq.  -ENOTSUP on pktios over several
+ * GPUs, as the plans: a shard's vector ranks start at zero. */
+struct mi_cls_vec_args;
+struct mi_cls_evrun;
+int odp_amd_cls_vec_fill(odp_pktio_t pktio, const struct mi_cls_vec_args *args, void *stream);
+int odp_amd_cls_vec_fill_host(odp_pktio_t pktio, const struct mi_cls_vec_args *args);
+int odp_amd_cls_vec_fill_host_submit(odp_pktio_t pktio, const struct mi_cls_vec_args *args, uint64_t *ticket);
+int odp_amd_cls_vec_fill_host_wait(odp_pktio_t pktio, uint64_t ticket);
+
+/* What the vector fill needs to know of the runtime's packet vectors: a
+ * vector's handle is its address, its size word lies *size_off and its table
+ * *tbl_off bytes behind it, and every vector of a page-locked vector pool
+ * inside [*varena_lo, *varena_lo + *varena_bytes).  0; -EINVAL (a NULL
+ * argument); -ENOENT when no vector pool is page-locked (the layout is still
+ * written). */
+int odp_amd_cls_vec_geom(uint32_t *size_off, uint32_t *tbl_off, uint64_t *varena_lo, uint64_t *varena_bytes);
+
+/* The vectors of a batch, one call per pool: min(need[s], what the pool has)
+ * vectors of vpools[s] (odp_amd_cls_runtab_fill's slots; need: the run plan's
+ * vec_need) into vgot[], slot s's at vbase[s] .. vbase[s] + vhave[s], one slot
+ * behind the other; vcap[s] the pool's max_size.  Slots at and past nslots
+ * get 0.  Returns the vectors taken (the fill's nvgot); -EINVAL: a NULL
+ * argument, nslots > 16 or a pool that is no packet-vector pool (nothing is
+ * kept); -ENOSPC: the pools' free vectors (this thread's
+ * view: another thread may take some meanwhile, then fewer are taken) would
+ * give more than vgot_cap (nothing is kept). */
+int odp_amd_cls_vec_take(const odp_pool_t vpools[], uint32_t nslots, const uint64_t need[],
+			 uint64_t vgot[], uint32_t vgot_cap, uint32_t vbase[], uint32_t vhave[],
+			 uint32_t vcap[]);
+
+/* The consumer of a filled batch: what _odp_cos_enq and _odp_cos_vector_enq
+ * do after the vectors are built, once per run and nothing per packet.  Run r
+ * < nruns: one odp_queue_enq_multi of ev[ev_first .. ev_first + ev_count) to
+ * dst_queue[dst] (to odp_queue_aggr(that, 0) for MI_CLS_RUN_AGGR) and the
+ * queue stats of _odp_cos_queue_stats_add: pk_enq packets, count - pk_enq
+ * discards.  A queue that takes fewer events than offered: a plain run's
+ * other packets are freed and counted as discards; a vector run counts vmax
+ * packets per vector taken (the reference's figure) and frees the other
+ * vectors with their packets.  Entries of value 0 (the move's holes, refused
+ * vectors) are left out of the enqueue -- ev is compacted in place -- and
+ * their packets counted as discards; a run whose remaining events the queue
+ * takes whole counts the packets in them exactly.  A refused vector's packets
+ * are freed when seq, ent (the fill's inputs) and ent_to_handle are given;
+ * with seq or ent NULL they stay the caller's to free (they are reachable
+ * through ent alone).  Vectors from odp_amd_cls_vec_take are never refused.
+ * Then one free call for lost[0 ..
+ * nlost), and the vectors taken and not used (vgot[vbase[s] + vec_used[s] ..
+ * vbase[s] + vhave[s])) go back to vpools[s].  rtab: the table the plan and
+ * the fill ran under.  Returns the events enqueued, or -EINVAL (a NULL
+ * argument, a destination id >= ndst; nothing is enqueued). */
+struct mi_cls_vec_out;
+int64_t odp_amd_cls_vec_enq(const struct mi_cls_run *runs, const struct mi_cls_evrun *evr, uint32_t nruns,
+			    uint64_t ev[], const uint64_t lost[], uint32_t nlost,
+			    const odp_queue_t dst_queue[], uint32_t ndst, const struct mi_cls_run_tab *rtab,
+			    const odp_pool_t vpools[], uint32_t nslots, const uint64_t vgot[],
+			    const uint32_t vbase[], const uint32_t vhave[], const struct mi_cls_vec_out *out,
+			    const uint32_t seq[], const uint64_t ent[], uint64_t ent_to_handle);
+
 /* Device contexts of the pktio (its GPUs, ODP_AMD_GPUS / create_multi); 1
  * for a single-device pktio, < 0 on error. */
 int odp_amd_cls_devices(odp_pktio_t pktio);

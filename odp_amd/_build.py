@@ -80,13 +80,13 @@ def build(force: bool = False, out_dir: str = PKG, defines=(), src_dir: str = SR
     host_deps = [asm_src, spec_src, prog_hdr, os.path.join(SRC, "mi_cls_asm.h"),
                  os.path.join(SRC, "mi_cls_spec.h")]
     k_srcs = [os.path.join(SRC, f"mi_cls_k{w}.hip") for w in (4, 8, 12, 16, "f", "f12", "f16", "c4",
-                                                              "c16", "d", "t", "h", "p", "l", "q", "r", "a", "m")]
+                                                              "c16", "d", "t", "h", "p", "l", "q", "r", "a", "m", "v")]
     tx_hdr = os.path.join(SRC, "mi_cls_tx_dev.h")
     parse_hdr = os.path.join(SRC, "mi_cls_parse_dev.h")
     lso_hdr = os.path.join(SRC, "mi_cls_lso_dev.h")
     enq_hdrs = [os.path.join(SRC, "mi_cls_enq_dev.h"), os.path.join(SRC, "mi_cls_rank_dev.h"),
                 os.path.join(SRC, "mi_cls_run_dev.h"), os.path.join(SRC, "mi_cls_pool_dev.h"),
-                os.path.join(SRC, "mi_cls_move_dev.h")]
+                os.path.join(SRC, "mi_cls_move_dev.h"), os.path.join(SRC, "mi_cls_vec_dev.h")]
     variant = bool(defines) or src_dir != globals()["SRC"]
     if force or variant or _stale(mi_so, [mi_src, mi_hdr, tx_hdr, parse_hdr, lso_hdr] + enq_hdrs + host_deps + k_srcs + hdrs + [__file__]):
         # one translation unit per block shape + the host code, compiled in
@@ -173,19 +173,41 @@ def build_test_drivers(force: bool = False):
     deps = [os.path.join(PKG, "libodp_cls.so"), os.path.join(PKG, "libodph.so"),
             os.path.join(INC, "odp_rt.h"), os.path.join(INC, "odp", "helper", "odph_api.h")]
     for name in ("rx_driver", "rt_unit", "tx_driver", "parse_driver", "lso_driver", "mq_driver",
-                 "runtab_driver", "pooltab_driver"):
+                 "runtab_driver", "pooltab_driver", "vecenq_unit", "vecfill_driver"):
         src = os.path.join(ROOT, "tests", "rt", name + ".c")
         if not os.path.exists(src):
             continue
         os.makedirs(TEST_BIN, exist_ok=True)
         out = os.path.join(TEST_BIN, name)
-        if not force and not _stale(out, [src] + deps):
+        # vecfill_driver includes rx_driver.c (its control plane and printing)
+        more = [os.path.join(ROOT, "tests", "rt", "rx_driver.c")] if name == "vecfill_driver" else []
+        if not force and not _stale(out, [src] + more + deps):
             continue
+        # vecenq_unit alone calls the kernel library's own entries (mi_cls_vec_fill)
+        mi = ["-lmi_cls"] if name == "vecenq_unit" else []
         _run(["gcc", "-O2", "-std=gnu11", "-Wall", "-I", INC, "-o", out, src, "-L", PKG,
-              "-lodph", "-lodp_cls", "-Wl,-rpath,$ORIGIN/" + os.path.relpath(PKG, TEST_BIN),
+              "-lodph", "-lodp_cls"] + mi + ["-Wl,-rpath,$ORIGIN/" + os.path.relpath(PKG, TEST_BIN),
               "-lpthread"])
         built = out
     return built
+
+
+def build_vecenq_sanitized(out_dir: str):
+    """tests/rt/vecenq_unit.c together with the runtime's C sources under
+    -fsanitize=address,undefined, as a stand-alone program in out_dir (never
+    in-tree): the memory-safety run of the vector fill's host side.  Needs no
+    device.  Run it with ASAN_OPTIONS=detect_leaks=0 (the HIP runtime that
+    libmi_cls.so loads keeps allocations of its own); it prints "ok".
+      python -c 'from odp_amd import _build as b; print(b.build_vecenq_sanitized("DIR"))'
+    """
+    os.makedirs(out_dir, exist_ok=True)
+    out = os.path.join(out_dir, "vecenq_unit_san")
+    srcs = [os.path.join(SRC, f) for f in ("odp_cls.c", "odp_rt.c", "odp_pktio.c", "odp_pktin.c", "odp_pktout.c",
+                                           "odp_pcap.c", "odph.c")]
+    _run(["gcc", "-O1", "-g", "-std=gnu11", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+          "-I", INC, "-I", SRC, "-o", out, os.path.join(ROOT, "tests", "rt", "vecenq_unit.c")] + srcs +
+         ["-L", PKG, "-lmi_cls", "-Wl,-rpath," + PKG, "-lpthread"])
+    return out
 
 
 EXAMPLE = os.path.join(ROOT, "oracle", "_ref", "odp_classifier")

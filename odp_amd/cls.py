@@ -302,6 +302,63 @@ def _move_host(L, prefix, handle, args, submit):
     return rc
 
 
+# the vector fill (include/mi_cls.h): the kernels' shape (a tile of runs or of
+# delivered places, the blocks' bound)
+VEC_TILE, VEC_GRID = 1024, 256
+VEC_NO_VECTOR = 0xFFFFFFFF      # vfirst of a run that got no vector
+EVRUN_DTYPE = np.dtype([("ev_first", "<u4"), ("ev_count", "<u4"), ("pk_enq", "<u4"), ("vfirst", "<u4")])
+
+
+class VecOut(C.Structure):
+    """mi_cls_vec_out_t."""
+    _fields_ = [("events", C.c_uint64), ("ev_span", C.c_uint64), ("vectors", C.c_uint64),
+                ("in_vectors", C.c_uint64), ("lost", C.c_uint64), ("holes", C.c_uint64),
+                ("refused", C.c_uint64), ("truncated", C.c_uint64), ("vec_used", C.c_uint64 * 16)]
+
+
+VEC_OUT_FIELDS = tuple(f[0] for f in VecOut._fields_[:8])
+VEC_OUT_WORDS = C.sizeof(VecOut) // 8
+
+
+class VecArgs(C.Structure):
+    """mi_cls_vec_args_t."""
+    _fields_ = [("seq", C.c_void_p), ("runs", C.c_void_p), ("run_out", C.c_void_p), ("ent", C.c_void_p),
+                ("vgot", C.c_void_p), ("n", C.c_uint32), ("run_cap", C.c_uint32), ("nvgot", C.c_uint32),
+                ("size_off", C.c_uint32), ("tbl_off", C.c_uint32), ("rsv", C.c_uint32),
+                ("ent_to_handle", C.c_uint64), ("rtab", C.c_void_p),
+                ("vbase", C.c_uint32 * 16), ("vhave", C.c_uint32 * 16), ("vcap", C.c_uint32 * 16),
+                ("varena_lo", C.c_uint64), ("varena_bytes", C.c_uint64),
+                ("ev", C.c_void_p), ("evr", C.c_void_p), ("lost", C.c_void_p), ("out", C.c_void_p)]
+
+
+def vec_args(rtab, vbase=(), vhave=(), vcap=(), **kw) -> VecArgs:
+    """A mi_cls_vec_args_t: rtab a RunTab (None: NULL), vbase / vhave / vcap
+    per slot (shorter sequences are padded with 0), every other field by
+    keyword -- pointers as ints (0 / None: NULL).  The table stays alive with
+    the returned struct."""
+    a = VecArgs()
+    if rtab is not None:
+        a.rtab = C.addressof(rtab)
+    a._rtab = rtab
+    for name, v in (("vbase", vbase), ("vhave", vhave), ("vcap", vcap)):
+        for k, x in enumerate(v):
+            getattr(a, name)[k] = int(x)
+    fields = dict(VecArgs._fields_)
+    for k, v in kw.items():
+        if k not in fields or k in ("rtab", "vbase", "vhave", "vcap"):
+            raise TypeError(f"vec_args: no field {k}")
+        setattr(a, k, v or None if fields[k] is C.c_void_p else int(v))
+    return a
+
+
+def vec_out_dict(words):
+    """The 24 uint64 of a mi_cls_vec_out_t as a dict (vec_used: a list)."""
+    w = [int(v) for v in words]
+    d = dict(zip(VEC_OUT_FIELDS, w))
+    d["vec_used"] = w[8:8 + RUN_VSLOTS]
+    return d
+
+
 def run_out_dict(words):
     """The 24 uint64 of a mi_cls_run_out_t as a dict (vec_need: a list)."""
     w = [int(v) for v in words]
@@ -444,6 +501,16 @@ def _load():
         "odp_amd_cls_pool_move_host_wait": (i32, [vp, C.c_uint64]),
         "odp_amd_cls_pool_move_geom": (i32, [C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_uint64),
                                              C.POINTER(C.c_uint64)]),
+        "mi_cls_vec_fill": (i32, [vp, C.POINTER(VecArgs), vp]),
+        "mi_cls_vec_fill_host": (i32, [vp, C.POINTER(VecArgs)]),
+        "mi_cls_vec_fill_host_submit": (i32, [vp, C.POINTER(VecArgs), C.POINTER(C.c_uint64)]),
+        "mi_cls_vec_fill_host_wait": (i32, [vp, C.c_uint64]),
+        "odp_amd_cls_vec_fill": (i32, [vp, C.POINTER(VecArgs), vp]),
+        "odp_amd_cls_vec_fill_host": (i32, [vp, C.POINTER(VecArgs)]),
+        "odp_amd_cls_vec_fill_host_submit": (i32, [vp, C.POINTER(VecArgs), C.POINTER(C.c_uint64)]),
+        "odp_amd_cls_vec_fill_host_wait": (i32, [vp, C.c_uint64]),
+        "odp_amd_cls_vec_geom": (i32, [C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64)]),
         "odp_amd_cls_parse_host": (i32, [vp, C.c_size_t, vp, vp, u32, u32, u32, u32, vp]),
         "odp_amd_cls_parse_term": (None, []),
     }
@@ -952,6 +1019,31 @@ class EnqContext(_FeatureContext):
         if rc != 0:
             raise RuntimeError(f"mi_cls_pool_move_host_wait: {rc}")
 
+    def fill_device(self, args, stream=0):
+        """mi_cls_vec_fill on a VecArgs of device pointers, stream-ordered.
+        Returns the C status."""
+        return self.L.mi_cls_vec_fill(self.ctx, C.byref(args), stream or None)
+
+    def fill(self, args):
+        """mi_cls_vec_fill on torch's current stream, waited for."""
+        import torch
+        dev = torch.device(f"cuda:{self.gpu}")
+        rc = self.fill_device(args, torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_vec_fill: {rc} ({lib().mi_cls_strerror(rc).decode()})")
+        torch.cuda.synchronize(dev)
+
+    def fill_host(self, args, submit=False):
+        """mi_cls_vec_fill_host on a VecArgs of host pointers (submit: the
+        _submit / _wait pair; "ticket": the _submit alone, returning the
+        ticket for fill_wait).  Returns the C status."""
+        return _move_host(self.L, "mi_cls_vec_fill_host", self.ctx, args, submit)
+
+    def fill_wait(self, ticket):
+        rc = self.L.mi_cls_vec_fill_host_wait(self.ctx, ticket)
+        if rc != 0:
+            raise RuntimeError(f"mi_cls_vec_fill_host_wait: {rc}")
+
     def plan_device(self, d_res, d_len, n, tab, d_perm, d_gbeg, d_out, stream=0):
         """On device pointers (ints), stream-ordered.  Returns the C status."""
         return self.L.mi_cls_enq_plan(self.ctx, d_res or None, d_len or None, n, C.byref(tab),
@@ -1359,6 +1451,25 @@ class Classifier:
         """odp_amd_cls_pool_move_host (submit: the _submit / _wait pair), as
         EnqContext.move_host."""
         return _move_host(self.L, "odp_amd_cls_pool_move_host", self.pktio, args, submit)
+
+    def vec_geom(self):
+        """odp_amd_cls_vec_geom: (rc, size_off, tbl_off, varena_lo,
+        varena_bytes)."""
+        so, to = C.c_uint32(), C.c_uint32()
+        lo, nb = C.c_uint64(), C.c_uint64()
+        rc = self.L.odp_amd_cls_vec_geom(C.byref(so), C.byref(to), C.byref(lo), C.byref(nb))
+        return rc, so.value, to.value, lo.value, nb.value
+
+    def vec_fill(self, args, stream=0):
+        """The vector fill of a planned batch (odp_amd_cls_vec_fill, on the
+        pktio's context) on a VecArgs of device pointers, stream-ordered.
+        Returns the C status."""
+        return self.L.odp_amd_cls_vec_fill(self.pktio, C.byref(args), stream or None)
+
+    def vec_fill_host(self, args, submit=False):
+        """odp_amd_cls_vec_fill_host (submit: the _submit / _wait pair), as
+        EnqContext.fill_host."""
+        return _move_host(self.L, "odp_amd_cls_vec_fill_host", self.pktio, args, submit)
 
     def cos_stats_packets(self, cos_handle):
         s = CosStats()

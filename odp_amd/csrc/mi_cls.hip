@@ -102,6 +102,19 @@ struct mi_cls_ctx {
 	hipEvent_t move_ev = nullptr;
 	hipStream_t move_last = nullptr;
 	bool move_used = false;
+	// the vector fill (mi_cls_vec_fill), likewise: the scratch of fixed size
+	// (the run table, the count matrix, the counters, the staged form's out),
+	// the scratch per run (vec_cap of them), the staged form's arrays in one
+	// buffer (vec_st_cap bytes), the run table's snapshot and whose copy the
+	// device holds
+	uint8_t *d_vec_fix = nullptr, *d_vec = nullptr, *d_vec_st = nullptr;
+	size_t vec_cap = 0, vec_st_cap = 0;
+	uint8_t *h_vec_tab = nullptr;
+	const void *vec_tab_src = nullptr;
+	uint64_t vec_tab_stamp = 0;
+	hipEvent_t vec_ev = nullptr;
+	hipStream_t vec_last = nullptr;
+	bool vec_used = false;
 	// program-specialised flat kernel for the loaded program (null: none)
 	std::shared_ptr<SpecCode> spec;
 	uint32_t batch_hint = 0; // largest batch per call (mi_cls_batch_hint), 0: unknown
@@ -193,6 +206,7 @@ static int preload_kernels(int device)
 	chk(mi_cls_launch_run(nullptr, RunArgs{}, true));
 	chk(mi_cls_launch_pool(nullptr, PoolArgs{}, true));
 	chk(mi_cls_launch_move(nullptr, MoveArgs{}, true));
+	chk(mi_cls_launch_vec(nullptr, VecArgs{}, true));
 	if (bad)
 		return bad;
 	done.insert(device);
@@ -311,6 +325,15 @@ extern "C" int mi_cls_ctx_destroy(mi_cls_ctx_t *c)
 	(void)hipFree(c->d_move_st);
 	if (c->h_move_tab)
 		(void)hipHostFree(c->h_move_tab);
+	if (c->vec_ev) {
+		(void)hipEventSynchronize(c->vec_ev);
+		(void)hipEventDestroy(c->vec_ev);
+	}
+	(void)hipFree(c->d_vec_fix);
+	(void)hipFree(c->d_vec);
+	(void)hipFree(c->d_vec_st);
+	if (c->h_vec_tab)
+		(void)hipHostFree(c->h_vec_tab);
 	(void)hipFree(c->d_rx);
 	if (c->h_tab)
 		(void)hipHostFree(c->h_tab);
@@ -2330,6 +2353,273 @@ extern "C" int mi_cls_pool_move_host_submit(mi_cls_ctx_t *c, const mi_cls_move_a
 }
 
 extern "C" int mi_cls_pool_move_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
+{
+	return feature_host_wait(c, ticket);
+}
+
+// ------------------------------------------------------------ the vector fill
+// The vector fill's scratch in the context, by the pool move's policy.  Of
+// fixed size: the run table's device copy, the count matrix, the counters and
+// the staged form's out.  Per run: 16 B (vec_cap runs, grown by 1.5x).  The
+// staged host form's arrays lie behind one another in a buffer of their own.
+#define VEC_FIX_RTAB 0u
+#define VEC_FIX_MAT (VEC_FIX_RTAB + ENQ_ALIGN(sizeof(mi_cls_run_tab_t)))
+#define VEC_FIX_CTR (VEC_FIX_MAT + ENQ_ALIGN((size_t)(MI_CLS_RUN_VSLOTS + 1u) * MI_CLS_VEC_GRID * 4u))
+#define VEC_FIX_OUT (VEC_FIX_CTR + ENQ_ALIGN(8u * 8u))
+#define VEC_FIX_ROUT (VEC_FIX_OUT + ENQ_ALIGN(sizeof(mi_cls_vec_out_t)))
+#define VEC_FIX_BYTES (VEC_FIX_ROUT + ENQ_ALIGN(sizeof(mi_cls_run_out_t)))
+#define VEC_WAVES_PER_BLOCK (MI_CLS_VEC_TILE / 64u)
+
+// Before the scratch is replaced, and before the table's snapshot or device
+// copy is rewritten, the previous fill has ended (vec_ev).
+static int vec_idle(mi_cls_ctx_t *c)
+{
+	if (c->vec_used)
+		HIP_OK(hipEventSynchronize(c->vec_ev));
+	return 0;
+}
+
+// nruns: the runs the device path keeps 16 B for; staged: bytes of the staged
+// host form (0: the device path)
+static int vec_scratch(mi_cls_ctx_t *c, uint32_t nruns, size_t staged)
+{
+	if (!c->d_vec_fix) {
+		if (!c->vec_ev && hipEventCreateWithFlags(&c->vec_ev, hipEventDisableTiming) != hipSuccess)
+			return -EIO;
+		if ((!c->h_vec_tab &&
+		     hipHostMalloc((void **)&c->h_vec_tab, sizeof(mi_cls_run_tab_t), hipHostMallocDefault) != hipSuccess) ||
+		    hipMalloc((void **)&c->d_vec_fix, VEC_FIX_BYTES) != hipSuccess)
+			return -ENOMEM;
+	}
+	if (nruns > c->vec_cap) {
+		const int rc = vec_idle(c);
+		if (rc)
+			return rc;
+		(void)hipFree(c->d_vec);
+		c->d_vec = nullptr;
+		c->vec_cap = 0;
+		const size_t cap = nruns < 4096u ? 4096u : (size_t)nruns + nruns / 2;
+		if (hipMalloc((void **)&c->d_vec, 16u * cap) != hipSuccess)
+			return -ENOMEM;
+		c->vec_cap = cap;
+	}
+	if (staged > c->vec_st_cap) {
+		const int rc = vec_idle(c);
+		if (rc)
+			return rc;
+		(void)hipFree(c->d_vec_st);
+		c->d_vec_st = nullptr;
+		c->vec_st_cap = 0;
+		const size_t cap = staged < 65536u ? 65536u : staged + staged / 2;
+		if (hipMalloc((void **)&c->d_vec_st, cap) != hipSuccess)
+			return -ENOMEM;
+		c->vec_st_cap = cap;
+	}
+	return 0;
+}
+
+// The table and the scalars first (host memory, no device needed), then the
+// context, then the batch
+static int vec_check(const mi_cls_ctx_t *c, const mi_cls_vec_args_t *a)
+{
+	if (!a || !a->rtab || a->n > MI_CLS_MAX_BATCH || (a->size_off & 3u) != 0 || (a->tbl_off & 7u) != 0 ||
+	    (uint64_t)a->size_off + 4u > a->tbl_off || a->varena_lo + a->varena_bytes < a->varena_lo ||
+	    (a->nvgot && !a->vgot))
+		return -EINVAL;
+	for (uint32_t s = 0; s < MI_CLS_RUN_VSLOTS; ++s)
+		if ((uint64_t)a->vbase[s] + a->vhave[s] > a->nvgot)
+			return -EINVAL;
+	for (uint32_t i = 0; i < 256u; ++i)
+		if ((a->rtab->mode[i] & MI_CLS_RUN_VEC) &&
+		    (a->rtab->vmax[i] == 0 || a->rtab->vslot[i] >= MI_CLS_RUN_VSLOTS ||
+		     a->rtab->vmax[i] > a->vcap[a->rtab->vslot[i]]))
+			return -EINVAL;
+	if (!c)
+		return no_ctx();
+	if (!a->out || ((uintptr_t)a->out & 7u) != 0)
+		return -EINVAL;
+	if (a->n == 0)
+		return 0;
+	if (a->run_cap && (!a->runs || !a->evr || (((uintptr_t)a->runs | (uintptr_t)a->evr) & 15u) != 0))
+		return -EINVAL;
+	return a->seq && a->run_out && a->ent && a->ev && a->lost &&
+			       (((uintptr_t)a->ent | (uintptr_t)a->vgot | (uintptr_t)a->ev | (uintptr_t)a->lost |
+				 (uintptr_t)a->run_out) & 7u) == 0 ? 0 : -EINVAL;
+}
+
+extern "C" int mi_cls_vec_fill(mi_cls_ctx_t *c, const mi_cls_vec_args_t *h, void *stream)
+{
+	int rc = vec_check(c, h);
+	if (rc)
+		return rc;
+	hipStream_t st = (hipStream_t)stream;
+	HIP_OK(set_device(c->device));
+	// the runs the kernels can meet: the true count is on the device
+	const uint32_t rb = h->run_cap < h->n ? h->run_cap : h->n;
+	rc = vec_scratch(c, rb, 0);
+	if (rc)
+		return rc;
+	// the scratch is one fill's at a time: a fill on another stream follows
+	// the previous one
+	if (c->vec_used && c->vec_last != st)
+		HIP_OK(hipStreamWaitEvent(st, c->vec_ev, 0));
+	const mi_cls_run_tab_t *rtab = h->rtab;
+	if (!c->vec_tab_src || c->vec_tab_src != rtab || c->vec_tab_stamp != rtab->stamp) {
+		rc = vec_idle(c);
+		if (rc)
+			return rc;
+		memcpy(c->h_vec_tab, rtab, sizeof(*rtab));
+		c->vec_tab_src = nullptr;
+		HIP_OK(hipMemcpyAsync(c->d_vec_fix + VEC_FIX_RTAB, c->h_vec_tab, sizeof(*rtab), hipMemcpyHostToDevice, st));
+		c->vec_tab_src = rtab;
+		c->vec_tab_stamp = ((const mi_cls_run_tab_t *)c->h_vec_tab)->stamp;
+	}
+	VecArgs a;
+	memset(&a, 0, sizeof(a));
+	a.seq = h->seq;
+	a.runs = h->runs;
+	a.rout = h->run_out;
+	a.ent = h->ent;
+	a.vgot = h->vgot;
+	a.rtab = (const mi_cls_run_tab_t *)(c->d_vec_fix + VEC_FIX_RTAB);
+	a.n = h->n;
+	a.run_cap = h->run_cap;
+	a.nvgot = h->nvgot;
+	a.size_off = h->size_off;
+	a.tbl_off = h->tbl_off;
+	{
+		const uint32_t tiles = (rb + MI_CLS_VEC_TILE - 1u) / MI_CLS_VEC_TILE;
+		a.grid = tiles < MI_CLS_VEC_GRID ? (tiles ? tiles : 1u) : MI_CLS_VEC_GRID;
+		a.tpb = (tiles + a.grid - 1u) / a.grid;
+		const uint32_t ftiles = (uint32_t)(((uint64_t)h->n + MI_CLS_VEC_TILE - 1u) / MI_CLS_VEC_TILE);
+		a.fgrid = ftiles < MI_CLS_VEC_GRID ? (ftiles ? ftiles : 1u) : MI_CLS_VEC_GRID;
+		a.ftpb = (ftiles + a.fgrid - 1u) / a.fgrid;
+	}
+	a.ent_to_handle = h->ent_to_handle;
+	a.varena_lo = h->varena_lo;
+	a.varena_bytes = h->varena_bytes;
+	memcpy(a.vbase, h->vbase, sizeof(a.vbase));
+	memcpy(a.vhave, h->vhave, sizeof(a.vhave));
+	a.mat = (uint32_t *)(c->d_vec_fix + VEC_FIX_MAT);
+	a.pl = (uint4 *)c->d_vec;
+	a.ctr = (unsigned long long *)(c->d_vec_fix + VEC_FIX_CTR);
+	a.ev = h->ev;
+	a.evr = h->evr;
+	a.lost = h->lost;
+	a.out = h->out;
+	// this call's counters start from zero, whatever the last one left
+	HIP_OK(hipMemsetAsync(a.ctr, 0, 8u * 8u, st));
+	uint32_t *last = c->last;
+	last[0] = 384u + VEC_WAVES_PER_BLOCK;
+	last[1] = h->n ? 4u : 1u;
+	last[2] = last[3] = last[4] = last[5] = 0;
+	last[6] = h->n ? a.fgrid : 0u;
+	rc = mi_cls_launch_vec(st, a, false);
+	if (rc)
+		return rc;
+	HIP_OK(hipEventRecord(c->vec_ev, st));
+	c->vec_used = true;
+	c->vec_last = st;
+	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+// The host forms' own condition: the vectors are worked on in place
+static int vec_host_check(const mi_cls_ctx_t *c, const mi_cls_vec_args_t *a)
+{
+	const int rc = vec_check(c, a);
+	if (rc)
+		return rc;
+	if (a->n == 0)
+		return 0;
+	return a->varena_bytes && mi_cls_host_mapped((const void *)(uintptr_t)a->varena_lo) &&
+			       mi_cls_host_mapped((const void *)(uintptr_t)(a->varena_lo + a->varena_bytes - 1u)) ? 0 : -EINVAL;
+}
+
+// A host batch on the context's stream, nothing waited for: in place when
+// every array is page-locked, else seq, runs, the run plan's out, ent and vgot
+// go up through the fill's staging buffer -- and ev, evr and lost with them, so
+// that what the fill leaves alone comes back as it was -- and ev, evr, lost
+// and out are copied back.
+static int vec_host_launch(mi_cls_ctx_t *c, const mi_cls_vec_args_t *h)
+{
+	HIP_OK(set_device(c->device));
+	mi_cls_vec_args_t a = *h;
+	const uint32_t n = h->n, cap = h->run_cap, nv = h->nvgot;
+	if (dev_views(a.out) && (n == 0 || (dev_views(a.seq, a.run_out, a.ent, a.ev, a.lost) &&
+					    (!cap || dev_views(a.runs, a.evr)) && (!nv || dev_views(a.vgot)))))
+		return mi_cls_vec_fill(c, &a, c->stream);
+	a = *h;
+	const size_t o_seq = 0, o_ent = o_seq + ENQ_ALIGN(4u * (size_t)n), o_ev = o_ent + ENQ_ALIGN(8u * (size_t)n),
+		     o_lost = o_ev + ENQ_ALIGN(8u * (size_t)n), o_runs = o_lost + ENQ_ALIGN(8u * (size_t)n),
+		     o_evr = o_runs + ENQ_ALIGN(16u * (size_t)cap), o_vgot = o_evr + ENQ_ALIGN(16u * (size_t)cap),
+		     bytes = o_vgot + ENQ_ALIGN(8u * (size_t)nv);
+	int rc = vec_scratch(c, 0, n ? bytes : 0);
+	if (rc)
+		return rc;
+	mi_cls_vec_out_t *dout = (mi_cls_vec_out_t *)(c->d_vec_fix + VEC_FIX_OUT);
+	uint8_t *d = c->d_vec_st;
+	if (n) {
+		// the staging buffer and the run plan's out in the scratch are the
+		// previous fill's until it has ended
+		if (c->vec_used && c->vec_last != c->stream)
+			HIP_OK(hipStreamWaitEvent(c->stream, c->vec_ev, 0));
+		HIP_OK(hipMemcpyAsync(d + o_seq, h->seq, 4u * (size_t)n, hipMemcpyHostToDevice, c->stream));
+		HIP_OK(hipMemcpyAsync(d + o_ent, h->ent, 8u * (size_t)n, hipMemcpyHostToDevice, c->stream));
+		HIP_OK(hipMemcpyAsync(d + o_ev, h->ev, 8u * (size_t)n, hipMemcpyHostToDevice, c->stream));
+		HIP_OK(hipMemcpyAsync(d + o_lost, h->lost, 8u * (size_t)n, hipMemcpyHostToDevice, c->stream));
+		if (cap) {
+			HIP_OK(hipMemcpyAsync(d + o_runs, h->runs, 16u * (size_t)cap, hipMemcpyHostToDevice, c->stream));
+			HIP_OK(hipMemcpyAsync(d + o_evr, h->evr, 16u * (size_t)cap, hipMemcpyHostToDevice, c->stream));
+		}
+		if (nv)
+			HIP_OK(hipMemcpyAsync(d + o_vgot, h->vgot, 8u * (size_t)nv, hipMemcpyHostToDevice, c->stream));
+		HIP_OK(hipMemcpyAsync(c->d_vec_fix + VEC_FIX_ROUT, h->run_out, sizeof(mi_cls_run_out_t),
+				      hipMemcpyHostToDevice, c->stream));
+		a.seq = (const uint32_t *)(d + o_seq);
+		a.ent = (const uint64_t *)(d + o_ent);
+		a.ev = (uint64_t *)(d + o_ev);
+		a.lost = (uint64_t *)(d + o_lost);
+		a.runs = cap ? (const mi_cls_run_t *)(d + o_runs) : nullptr;
+		a.evr = cap ? (mi_cls_evrun_t *)(d + o_evr) : nullptr;
+		a.vgot = nv ? (const uint64_t *)(d + o_vgot) : nullptr;
+		a.run_out = (const mi_cls_run_out_t *)(c->d_vec_fix + VEC_FIX_ROUT);
+	}
+	a.out = dout;
+	rc = mi_cls_vec_fill(c, &a, c->stream);
+	if (rc)
+		return rc;
+	if (n) {
+		HIP_OK(hipMemcpyAsync(h->ev, d + o_ev, 8u * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+		HIP_OK(hipMemcpyAsync(h->lost, d + o_lost, 8u * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+		if (cap)
+			HIP_OK(hipMemcpyAsync(h->evr, d + o_evr, 16u * (size_t)cap, hipMemcpyDeviceToHost, c->stream));
+	}
+	HIP_OK(hipMemcpyAsync(h->out, dout, sizeof(*dout), hipMemcpyDeviceToHost, c->stream));
+	// the scratch is this fill's until the copies have read it
+	HIP_OK(hipEventRecord(c->vec_ev, c->stream));
+	return 0;
+}
+
+extern "C" int mi_cls_vec_fill_host(mi_cls_ctx_t *c, const mi_cls_vec_args_t *a)
+{
+	const int rc = vec_host_check(c, a);
+	if (rc)
+		return rc;
+	return host_run(c, nullptr, [&] { return vec_host_launch(c, a); });
+}
+
+extern "C" int mi_cls_vec_fill_host_submit(mi_cls_ctx_t *c, const mi_cls_vec_args_t *a, uint64_t *ticket)
+{
+	if (!ticket)
+		return -EINVAL;
+	*ticket = 0;
+	const int rc = vec_host_check(c, a);
+	if (rc)
+		return rc;
+	return host_run(c, ticket, [&] { return vec_host_launch(c, a); });
+}
+
+extern "C" int mi_cls_vec_fill_host_wait(mi_cls_ctx_t *c, uint64_t ticket)
 {
 	return feature_host_wait(c, ticket);
 }

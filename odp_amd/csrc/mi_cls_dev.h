@@ -3031,6 +3031,39 @@ struct MoveArgs {
 // alone.  preload: resolve the kernels only.
 int mi_cls_launch_move(hipStream_t st, const MoveArgs &a, bool preload);
 
+// the vector fill (mi_cls_vec_fill; kernels: mi_cls_vec_dev.h, mi_cls_kv.hip)
+struct VecArgs {
+	const uint32_t *seq;
+	const mi_cls_run_t *runs;
+	const mi_cls_run_out_t *rout;  // the run plan's out: nruns and delivered, read by every launch
+	const uint64_t *ent;
+	const uint64_t *vgot;
+	const mi_cls_run_tab_t *rtab;  // the device copy
+	uint32_t n;
+	uint32_t run_cap;
+	uint32_t nvgot;
+	uint32_t size_off, tbl_off;
+	uint32_t grid;                 // blocks of the count and place launches (over runs)
+	uint32_t tpb;                  // their tiles per block
+	uint32_t fgrid;                // blocks of the fill launch (over delivered places)
+	uint32_t ftpb;                 // its tiles per block
+	uint32_t rsv;
+	uint64_t ent_to_handle;
+	uint64_t varena_lo, varena_bytes;
+	uint32_t vbase[MI_CLS_RUN_VSLOTS];
+	uint32_t vhave[MI_CLS_RUN_VSLOTS];
+	uint32_t *mat;                 // scratch: (MI_CLS_RUN_VSLOTS + 1) x grid sums, row-major by slot
+	uint4 *pl;                     // scratch: per run ev_first, g, vfirst, the clamped count
+	unsigned long long *ctr;       // scratch: the counters, zeroed before the launches
+	uint64_t *ev;
+	mi_cls_evrun_t *evr;
+	uint64_t *lost;
+	mi_cls_vec_out_t *out;
+};
+// The vector fill's launches on `st`, in order: count, place, fill, finish;
+// n == 0: finish alone.  preload: resolve the kernels only.
+int mi_cls_launch_vec(hipStream_t st, const VecArgs &a, bool preload);
+
 // Every launcher goes through mi_launch.  grid == 0 launches nothing: it
 // resolves the instantiation on the current device (hipFuncGetAttributes
 // loads the code object that holds it), so mi_cls_ctx_create can load every

@@ -1737,6 +1737,45 @@ int odp_amd_cls_pool_move_host_wait(odp_pktio_t h, uint64_t ticket)
 	return ticket && e->ctx ? mi_cls_pool_move_host_wait(e->ctx, ticket) : ticket ? -EINVAL : 0;
 }
 
+/* The vector fill (mi_cls_vec_fill and its host forms) on the pktio's context:
+ * -ENOTSUP over several GPUs, as the pool plan. */
+int odp_amd_cls_vec_fill(odp_pktio_t h, const struct mi_cls_vec_args *args, void *stream)
+{
+	mi_cls_ctx_t *c;
+	const int rc = enq_ctx(h, &c);
+
+	return rc ? rc : mi_cls_vec_fill(c, args, stream);
+}
+
+int odp_amd_cls_vec_fill_host(odp_pktio_t h, const struct mi_cls_vec_args *args)
+{
+	mi_cls_ctx_t *c;
+	const int rc = enq_ctx(h, &c);
+
+	return rc ? rc : mi_cls_vec_fill_host(c, args);
+}
+
+int odp_amd_cls_vec_fill_host_submit(odp_pktio_t h, const struct mi_cls_vec_args *args, uint64_t *ticket)
+{
+	mi_cls_ctx_t *c;
+	int rc;
+
+	if (!ticket)
+		return -EINVAL;
+	*ticket = 0;
+	rc = enq_ctx(h, &c);
+	return rc ? rc : mi_cls_vec_fill_host_submit(c, args, ticket);
+}
+
+int odp_amd_cls_vec_fill_host_wait(odp_pktio_t h, uint64_t ticket)
+{
+	pktio_t *e = get_pktio(h);
+
+	if (!e)
+		return -EINVAL;
+	return ticket && e->ctx ? mi_cls_vec_fill_host_wait(e->ctx, ticket) : ticket ? -EINVAL : 0;
+}
+
 /* One burst's receive chain (mi_cls_rx_chain_submit) on the pktio's
  * context, under the current rules.  -ENOTSUP for pktios over several
  * devices (they take the host-decided delivery). */

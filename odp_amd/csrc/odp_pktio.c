@@ -342,6 +342,209 @@ int odp_amd_cls_pool_move_geom(uint32_t *meta_off, uint32_t *data_from_meta, uin
 	return 0;
 }
 
+/* The vector fill's geometry: the runtime's packet-vector layout (a vector's
+ * handle is its header's address) and the one range all page-locked vector
+ * pools lie in.  -ENOENT when there is none. */
+int odp_amd_cls_vec_geom(uint32_t *size_off, uint32_t *tbl_off, uint64_t *varena_lo, uint64_t *varena_bytes)
+{
+	uint8_t *lo;
+	size_t span;
+
+	if (!size_off || !tbl_off || !varena_lo || !varena_bytes)
+		return -EINVAL;
+	*size_off = (uint32_t)__builtin_offsetof(evv_hdr_t, size);
+	*tbl_off = (uint32_t)__builtin_offsetof(evv_hdr_t, tbl);
+	*varena_lo = 0;
+	*varena_bytes = 0;
+	if (!rt_vec_arena(&lo, &span))
+		return -ENOENT;
+	*varena_lo = (uint64_t)(uintptr_t)lo;
+	*varena_bytes = span;
+	return 0;
+}
+
+int odp_amd_cls_vec_take(const odp_pool_t vpools[], uint32_t nslots, const uint64_t need[],
+			 uint64_t vgot[], uint32_t vgot_cap, uint32_t vbase[], uint32_t vhave[],
+			 uint32_t vcap[])
+{
+	uint64_t want = 0;
+	uint32_t at = 0;
+
+	if (!need || !vbase || !vhave || !vcap || (nslots && !vpools) || nslots > MI_CLS_RUN_VSLOTS)
+		return -EINVAL;
+	for (uint32_t s = 0; s < nslots; s++) {
+		const rt_pool_t *p = rt_pool(vpools[s]);
+
+		if (!p || p->param.type != ODP_POOL_VECTOR)
+			return -EINVAL;
+		const uint32_t avail = rt_pool_avail(vpools[s]);
+
+		want += need[s] < avail ? need[s] : avail;
+	}
+	if (want > vgot_cap || (want && !vgot))
+		return -ENOSPC;
+	for (uint32_t s = 0; s < MI_CLS_RUN_VSLOTS; s++) {
+		vbase[s] = at;
+		vhave[s] = 0;
+		vcap[s] = 0;
+		if (s >= nslots)
+			continue;
+		const rt_pool_t *p = rt_pool(vpools[s]);
+		const uint32_t avail = rt_pool_avail(vpools[s]);
+		const uint64_t w = need[s] < avail ? need[s] : avail;
+
+		vcap[s] = p->data_cap;
+		if (w)
+			vhave[s] = (uint32_t)rt_vector_alloc_raw(vpools[s], (odp_event_t *)(void *)(vgot + at), (int)w);
+		at += vhave[s];
+	}
+	return (int)at;
+}
+
+/* Queue slot of dst inside the CoS (_odp_cos_queue_idx,
+ * odp_classification_internal.h:49-65): 0 for a single-queue CoS. */
+static uint32_t vec_cos_slot(uint32_t cos_index, odp_queue_t dst)
+{
+	odp_cos_t cos = (odp_cos_t)(uintptr_t)(cos_index + 1u);
+	uint32_t nq = odp_cls_cos_num_queue(cos), slot = 0;
+
+	if (nq > 1) {
+		odp_queue_t qs[32];
+
+		odp_cls_cos_queues(cos, qs, 32);
+		for (uint32_t i = 0; i < nq && i < 32; i++)
+			if (qs[i] == dst)
+				slot = i;
+	}
+	return slot;
+}
+
+/* The entries of value 0 taken out of e[0..n), order kept; returns the rest */
+static uint32_t vec_compact(uint64_t e[], uint32_t n)
+{
+	uint32_t k = 0;
+
+	while (k < n && e[k])
+		k++;
+	for (uint32_t i = k; i < n; i++)
+		if (e[i])
+			e[k++] = e[i];
+	return k;
+}
+
+int64_t odp_amd_cls_vec_enq(const struct mi_cls_run *runs, const struct mi_cls_evrun *evr, uint32_t nruns,
+			    uint64_t ev[], const uint64_t lost[], uint32_t nlost,
+			    const odp_queue_t dst_queue[], uint32_t ndst, const struct mi_cls_run_tab *rtab,
+			    const odp_pool_t vpools[], uint32_t nslots, const uint64_t vgot[],
+			    const uint32_t vbase[], const uint32_t vhave[], const struct mi_cls_vec_out *out,
+			    const uint32_t seq[], const uint64_t ent[], uint64_t ent_to_handle)
+{
+	int64_t events = 0;
+
+	if ((nruns && (!runs || !evr || !ev || !dst_queue)) || (nlost && !lost) || !rtab || !out ||
+	    (nslots && (!vpools || !vbase || !vhave)) || nslots > MI_CLS_RUN_VSLOTS)
+		return -EINVAL;
+	for (uint32_t r = 0; r < nruns; r++)
+		if (runs[r].dst >= ndst)
+			return -EINVAL;
+	for (uint32_t r = 0; r < nruns; r++) {
+		const mi_cls_run_t *u = &runs[r];
+		const mi_cls_evrun_t *x = &evr[r];
+		const odp_queue_t dst = dst_queue[u->dst];
+		const uint32_t slot = vec_cos_slot(u->cos, dst);
+		odp_event_t *e = (odp_event_t *)(void *)(ev + x->ev_first);
+		const int vec = (u->flags & MI_CLS_RUN_VEC) != 0;
+		const uint32_t vm = rtab->vmax[u->cos] ? rtab->vmax[u->cos] : 1u;
+		uint64_t refused_pk = 0;
+		int ret;
+
+		/* a refused vector (entry 0 among the run's ev_count): its packets were
+		 * put nowhere; with seq and ent they are freed here, else they stay the
+		 * caller's (reachable through ent).  Discards either way. */
+		for (uint32_t k = 0; vec && k < x->ev_count; k++) {
+			if (e[k])
+				continue;
+			const uint32_t at = k * vm, sz = u->count - at < vm ? u->count - at : vm;
+
+			refused_pk += sz;
+			for (uint32_t j = 0; seq && ent && j < sz; j++) {
+				const uint64_t l = ent[seq[u->first + at + j]];
+
+				if (l)
+					odp_packet_free((odp_packet_t)(uintptr_t)(l - ent_to_handle));
+			}
+		}
+		const uint32_t num = vec_compact(ev + x->ev_first, x->ev_count);
+
+		if (!vec) {
+			const odp_queue_t q = (u->flags & MI_CLS_RUN_AGGR) ? odp_queue_aggr(dst, 0) : dst;
+
+			ret = num && q != ODP_QUEUE_INVALID ? odp_queue_enq_multi(q, e, (int)num) : 0;
+			if (ret < 0)
+				ret = 0;
+			if ((uint32_t)ret != num)
+				odp_packet_free_multi((const odp_packet_t *)(void *)(e + ret), (int)num - ret);
+			odp_amd_cls_queue_stats_add(u->cos, slot, (uint64_t)ret, (uint64_t)u->count - (uint64_t)ret);
+			events += ret;
+			continue;
+		}
+		if (num == 0) {   /* no vector: the run's packets are in lost[] (or were refused) */
+			odp_amd_cls_queue_stats_add(u->cos, slot, 0, u->count);
+			continue;
+		}
+		ret = dst != ODP_QUEUE_INVALID ? odp_queue_enq_multi(dst, e, (int)num) : -1;
+		if ((uint32_t)ret == num) {   /* the queue took what was offered */
+			const uint64_t enq = x->pk_enq - refused_pk;
+
+			odp_amd_cls_queue_stats_add(u->cos, slot, enq, (uint64_t)u->count - enq);
+			events += ret;
+			continue;
+		}
+		if (ret < 0)
+			ret = 0;
+		/* the reference's figure (odp_classification_internal.h:125-129) */
+		uint64_t enq = (uint64_t)vm * (uint32_t)ret;
+
+		if (enq > u->count)
+			enq = u->count;
+		odp_amd_cls_queue_stats_add(u->cos, slot, enq, (uint64_t)u->count - enq);
+		events += ret;
+		for (uint32_t i = (uint32_t)ret; i < num; i++) {
+			odp_packet_vector_t pv = odp_packet_vector_from_event(e[i]);
+			odp_packet_t *tbl;
+			uint32_t sz = odp_packet_vector_tbl(pv, &tbl);
+
+			sz = vec_compact((uint64_t *)(void *)tbl, sz);
+			odp_packet_free_multi(tbl, (int)sz);
+			odp_packet_vector_free(pv);
+		}
+	}
+	/* one free call for the lost packets; in pieces only to leave out holes */
+	if (out->holes == 0 && nlost) {
+		odp_packet_free_multi((const odp_packet_t *)(const void *)lost, (int)nlost);
+		nlost = 0;
+	}
+	for (uint32_t i = 0; i < nlost;) {
+		odp_packet_t pk[256];
+		int k = 0;
+
+		while (i < nlost && k < 256) {
+			if (lost[i])
+				pk[k++] = (odp_packet_t)(uintptr_t)lost[i];
+			i++;
+		}
+		odp_packet_free_multi(pk, k);
+	}
+	for (uint32_t s = 0; s < nslots; s++) {
+		const uint64_t used = out->vec_used[s] < vhave[s] ? out->vec_used[s] : vhave[s];
+
+		if (used < vhave[s])
+			rt_packet_return_raw(vpools[s], (const odp_packet_t *)(const void *)(vgot + vbase[s] + used),
+					     (int)(vhave[s] - used));
+	}
+	return events;
+}
+
 odp_pktio_t odp_pktio_lookup(const char *name)
 {
 	for (int i = 0; i < RT_MAX_PKTIO; i++)

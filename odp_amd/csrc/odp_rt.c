@@ -588,6 +588,25 @@ int rt_pinned_arena(uint8_t **lo, size_t *bytes)
 	return a != NULL;
 }
 
+int rt_vec_arena(uint8_t **lo, size_t *bytes)
+{
+	uint8_t *a = NULL, *b = NULL;
+
+	for (int i = 0; i < RT_MAX_POOLS; i++) {
+		const rt_pool_t *p = &RT.pool[i];
+
+		if (!p->used || !p->vpinned || !p->mem)
+			continue;
+		if (!a || p->mem < a)
+			a = p->mem;
+		if (!b || p->mem + p->elem_size * p->num > b)
+			b = p->mem + p->elem_size * p->num;
+	}
+	*lo = a;
+	*bytes = a ? (size_t)(b - a) : 0;
+	return a != NULL;
+}
+
 uint32_t rt_data_from_meta(void)
 {
 	return (uint32_t)(align_up(sizeof(pkt_hdr_t), 64) + RT_PKT_HEADROOM -
@@ -669,6 +688,16 @@ odp_pool_t odp_pool_create(const char *name, const odp_pool_param_t *param)
 		}
 		p->pinned = mem != NULL;
 	}
+	/* packet-vector pools likewise, under the same switches: the vector fill
+	 * writes the vectors' tables and sizes from the GPU */
+	if (param->type == ODP_POOL_VECTOR && pinned_pools() && !pool_pageable(name)) {
+		mem = mi_cls_host_alloc(esz * num);
+		if (mem && !mi_cls_host_mapped(mem)) {
+			mi_cls_host_free(mem);
+			mem = NULL;
+		}
+		p->vpinned = mem != NULL;
+	}
 	if (!mem && posix_memalign(&mem, 64, esz * num)) {
 		p->used = 0;
 		return ODP_POOL_INVALID;
@@ -682,7 +711,7 @@ odp_pool_t odp_pool_create(const char *name, const odp_pool_param_t *param)
 	odp_spinlock_init(&p->lock);
 	p->free_stk = malloc((size_t)num * sizeof(ev_hdr_t *));
 	if (!p->free_stk) {
-		if (p->pinned)
+		if (p->pinned || p->vpinned)
 			mi_cls_host_free(p->mem);
 		else
 			free(p->mem);
@@ -721,7 +750,7 @@ int odp_pool_destroy(odp_pool_t h)
 	pool_cache_flush((int)(p - RT.pool));
 	if (p->num_free != p->num)
 		RT_ERR("pool %s destroyed with %u events in use\n", p->name, p->num - p->num_free);
-	if (p->pinned)
+	if (p->pinned || p->vpinned)
 		mi_cls_host_free(p->mem);
 	else
 		free(p->mem);
@@ -995,6 +1024,15 @@ int rt_packet_alloc_raw(odp_pool_t pool, uint32_t len, odp_packet_t pkt[], int n
 	if (!p || p->param.type != ODP_POOL_PACKET || len > p->data_cap || num <= 0)
 		return 0;
 	return pool_alloc(p, (ev_hdr_t **)(void *)pkt, num);
+}
+
+int rt_vector_alloc_raw(odp_pool_t pool, odp_event_t v[], int num)
+{
+	rt_pool_t *p = rt_pool(pool);
+
+	if (!p || p->param.type != ODP_POOL_VECTOR || num <= 0)
+		return 0;
+	return pool_alloc(p, (ev_hdr_t **)(void *)v, num);
 }
 
 /* Packets of one pool back to it at once (taken with rt_packet_alloc_raw and

@@ -121,6 +121,9 @@ typedef struct rt_pool {
 	uint32_t gen;           /* creation number: tags the thread caches */
 	int pinned;             /* mem is page-locked and device-addressed at its host
 				 * addresses (GPU receive delivery reads / writes it) */
+	int vpinned;            /* the same for a packet-vector pool (the vector fill
+				 * writes its vectors); kept apart from `pinned`, which
+				 * speaks of packets alone */
 	odp_spinlock_t lock;
 } rt_pool_t;
 
@@ -181,5 +184,11 @@ int rt_pinned_handles(const odp_packet_t pk[], int n);
 /* bytes from a packet header's metadata block to its data at the default
  * headroom (fixed by the pool layout) */
 uint32_t rt_data_from_meta(void);
+/* the address range spanned by the page-locked packet-vector pools; 0 when
+ * there is none */
+int rt_vec_arena(uint8_t **lo, size_t *bytes);
+/* up to num vectors of an ODP_POOL_VECTOR pool with one call, sizes not set;
+ * returns the count taken.  rt_packet_return_raw gives unused ones back. */
+int rt_vector_alloc_raw(odp_pool_t pool, odp_event_t v[], int num);
 
 #endif /* ODP_AMD_RT_INTERNAL_H_ */
